@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the Semi-DETR hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is ONE pass of the hot path of a Semi-DETR teacher-student training iteration for one GPU's share
@@ -19,7 +19,10 @@ SURVEY.md section 3.1), on synthetic inputs already resident in HBM:
 
 The dense parts of the model (ResNet-50, Linear/FFN GEMMs) are NOT in the step: this run measures the hot
 path the north star names, not the whole detector.  `value` = images/s of that path over all ranks.
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Rank 0 prints ONE JSON line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed step) and the
+`roofline` of the timed steps' dominant kernel.  A plain run sets up, warms up, times K steps and prints that line; `--full`
+adds everything that takes runs of its own (micro-benchmarks, other step flavours, `cpu_baseline`, ...).
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs) for output-by-output comparisons.
 """
 import argparse
 import json
@@ -27,6 +30,7 @@ import math
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -264,6 +268,7 @@ class Workload:
         self.groups = {}
         self.events = []
         self.kernels = {}          # event group -> device kernels the library reports for it
+        self.capture = None        # a dict: every call site of the next steps leaves what it returned there (--dump-outputs)
 
     def alg_bytes(self, n, lq, backward):
         return msda_alg_bytes(n, lq, backward, self.S, self.L)
@@ -294,15 +299,18 @@ class Workload:
         mask = self.mask[n] if self.masked else None
         mask4 = mask[..., None, None] if self.masked else None
 
+        name = f"msda_fwd_{kind}_bs{n}_Lq{lq}"
+
         def run():
             for v, a in calls:
                 if not self.masked:
-                    fn(v, self.shapes, self.starts, *a, *im2col)
+                    out = fn(v, self.shapes, self.starts, *a, *im2col)
                 elif self.io == "raw":
-                    fn(v, self.shapes, self.starts, *a, mask)
+                    out = fn(v, self.shapes, self.starts, *a, mask)
                 else:      # ops/modules/ms_deform_attn.py:95-96
-                    fn(v.masked_fill(mask4, 0.0), self.shapes, self.starts, *a, *im2col)
-        name = f"msda_fwd_{kind}_bs{n}_Lq{lq}"
+                    out = fn(v.masked_fill(mask4, 0.0), self.shapes, self.starts, *a, *im2col)
+            if self.capture is not None:      # the last layer's output (every pass of a group reads the same input sets)
+                self.capture[name] = out
         self._timed(name, reps, self.alg_bytes(n, lq, False), run)
         # (every time: the encoder forward's kernel is chosen from the data of the previous launches, the last call wins)
         self.kernels[name] = self.sda._lib.lib().semidetr_msda_last_kernels().decode().split("+")
@@ -317,15 +325,21 @@ class Workload:
         mask = self.mask[n] if self.masked else None
         mask4 = mask[..., None, None] if self.masked else None
 
+        name = f"msda_bwd_{kind}_bs{n}_Lq{lq}"
+        grads = ("grad_value", "grad_offsets", "grad_logits") if self.io == "raw" else ("grad_value", "grad_loc", "grad_attn")
+
         def run():
             for v, a, go in calls:
                 if not self.masked:
-                    fn(v, self.shapes, self.starts, *a, go, *im2col)
+                    out = fn(v, self.shapes, self.starts, *a, go, *im2col)
                 elif self.io == "raw":
-                    fn(v, self.shapes, self.starts, *a, go, mask)
+                    out = fn(v, self.shapes, self.starts, *a, go, mask)
                 else:      # the op on the masked copy autograd saved, then masked_fill's backward on grad_value
-                    fn(v, self.shapes, self.starts, *a, go, *im2col)[0].masked_fill(mask4, 0.0)
-        name = f"msda_bwd_{kind}_bs{n}_Lq{lq}"
+                    out = fn(v, self.shapes, self.starts, *a, go, *im2col)
+                    out = [out[0].masked_fill(mask4, 0.0)] + list(out[1:])
+            if self.capture is not None:
+                for g, t in zip(grads, out):
+                    self.capture[name + "_" + g] = t
         self._timed(name, reps, self.alg_bytes(n, lq, True), run)
         if name not in self.kernels:
             self.kernels[name] = self.sda._lib.lib().semidetr_msda_last_kernels().decode().split("+")
@@ -336,12 +350,20 @@ class Workload:
 
     def _pseudo_finish(self):
         boxes, labels, scores = self.pending.result()
-        self.sda.transform_bboxes(boxes, self.warp, [m["img_shape"] for m in self.t_metas])
+        warped = self.sda.transform_bboxes(boxes, self.warp, [m["img_shape"] for m in self.t_metas])
+        if self.capture is not None:      # the per-image lists, concatenated, and how many boxes each image kept
+            self.capture.update(pseudo_boxes=torch.cat(boxes), pseudo_labels=torch.cat(labels), pseudo_scores=torch.cat(scores),
+                                pseudo_counts=torch.tensor([len(b) for b in boxes]), pseudo_boxes_warped=torch.cat(warped))
 
     def _match(self, i):
         bp, cp, gts, labs, metas = self.match_sets[i]
-        self._timed("hungarian_batch", 1, 0,
-                    lambda: self.asg.assign_batch(bp, cp, gts, labs, metas, check=False))
+
+        def run():
+            res = self.asg.assign_batch(bp, cp, gts, labs, metas, check=False)
+            if self.capture is not None:
+                for f in ("gt_inds", "labels"):      # (max_overlaps is None for this assigner, as in the reference)
+                    self.capture["hungarian_%d_%s" % (i, f)] = torch.stack([getattr(r, f) for r in res])
+        self._timed("hungarian_batch", 1, 0, run)
 
     def step(self, ddp=None, record=False, reuse_encoder=False, backbone_cycles=0):
         """`ddp`: the dp.FlatDDP wrapper of the student's parameter list (None on one GPU).  The MSDA backward launches
@@ -958,11 +980,45 @@ def run_flavour(dev, seed, recipe, io, steps=5, warmup=2, reuse_encoder=False, i
     return res
 
 
+DUMP_SAMPLE = 1 << 19                                       # --dump-outputs: elements kept of a larger array (fixed seeded sample)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs DIR: what the last timed step handed its callers, one DIR/<name>.npy each -- every MSDA group's last
+    forward output and backward gradients, the pseudo-label lists (concatenated) and their warped boxes, the Hungarian
+    assignments, and the EMA teacher parameters (concatenated).  Floating point stays float32, integers become float64.
+    An array larger than DUMP_SAMPLE elements is flattened and sampled at DUMP_SAMPLE positions drawn from a generator
+    seeded with its name, so two builds run with the same arguments write comparable files."""
+    arrays = dict(wl.capture, ema_teacher=torch.cat([t.reshape(-1) for t in wl.teacher]))
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name in sorted(arrays):
+        t = arrays[name].detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), DUMP_SAMPLE, replace=False)
+            t = t.reshape(-1)[torch.from_numpy(np.sort(idx)).to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise RuntimeError("--dump-outputs: more than %d bytes (at %s)" % (DUMP_LIMIT_BYTES, name))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(arrays), total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures (one GPU, headline configuration): the "
+                         "supervised step, the MSDA micro-benchmark, the encoder forward by sample spread, the module level, the "
+                         "warm-up stage, the other step flavours and the CPU baseline; --no-micro / --no-flavours / "
+                         "--no-cpu-baseline leave parts out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-micro", action="store_true")
     ap.add_argument("--recipe", default="coco10", choices=sorted(RECIPES),
@@ -1058,13 +1114,19 @@ def main():
     coll.update(all_reduce=0, all_reduce_bytes=0, other=0)
     comm_prof = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            wl.capture = {}
         wl.step(ddp, record=True, **kw)
         if ddp is not None:
             comm_prof.append(ddp._last_stamps)       # resolved after the timed region (reading an event synchronises)
     barrier()
     elapsed = time.perf_counter() - t0
     coll_timed = dict(coll)
+    if args.dump_outputs and rank == 0:
+        n_dump, dump_bytes = dump_outputs(wl, args.dump_outputs)
+        print("bench: %d arrays, %.1f MB -> %s" % (n_dump, dump_bytes / 1e6, args.dump_outputs), file=sys.stderr)
+    wl.capture = None
     t_hold = time.perf_counter()
     while args.hold > 0 and time.perf_counter() - t_hold < args.hold:      # untimed: lets a GPU-busy sampler see the device
         wl.step(ddp, **kw)
@@ -1196,7 +1258,8 @@ def main():
                         "backward runs behind it); --backbone-ms X puts a device-side sleep of X ms there, the backbone's "
                         "parameters becoming ready in four slices (realistic)"}
         headline_cfg = args.recipe == "coco10" and args.io == "raw" and args.masked and not args.reuse_encoder
-        if world == 1 and not args.no_micro and headline_cfg:      # single-GPU extras
+        # everything below takes runs of its own: only with --full (a plain run stops at the headline)
+        if world == 1 and args.full and not args.no_micro and headline_cfg:      # single-GPU extras
             # BASELINE.json config 2: supervised DINO-R50 bs 2 (hot path only), its own timed loop
             for _ in range(2):
                 wl.sup_step()
@@ -1229,7 +1292,7 @@ def main():
             out["encoder_forward_by_sample_spread"] = forward_policy_bench(dev)
             out["module_fused_prologue"] = module_bench(dev)
             out["warmup_stage"] = warmup_stage_bench(dev)
-        if world == 1 and not args.no_flavours and headline_cfg:
+        if world == 1 and args.full and not args.no_flavours and headline_cfg:
             # the other flavours of the step, 5 steps each (the driver's record then answers "COCO-Full images/s" and
             # "reference-contract images/s" by itself); the headline above is the PRODUCT DEFAULT: fused prologue + padding mask
             del wl.t
@@ -1257,7 +1320,7 @@ def main():
                                        "headline configuration, NOT the reference's call structure; replayed_inputs = the locattn step "
                                        "with ONE input set per group replayed by all six layers (--input-sets 1), the methodology of "
                                        "rounds 1-3: comparable with BENCH_r01..r03 only")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl)
         print(json.dumps(out))
     if world > 1:

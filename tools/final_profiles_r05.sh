@@ -2,6 +2,7 @@
 # Round-5 refresh on the GPU box: traffic JSON + TA evidence (rocprofv3 --pmc passes), the full GPU suite, smoke, the default
 # bench line (with its flavours), the rocprofv3 kernel statistics of the bench command, a 2-rank line (gloo, one GPU: the N > 1 keys).
 R=${GRAFT_REPO_ROOT:-/root/repo}
+O=${BENCH_OUT:-bench_out}; mkdir -p $R/$O      # the bench lines go here (relative to the repository root)
 cd $R && mkdir -p gpurun_out
 timeout -k 5 1500 python tools/measure_traffic.py > gpurun_out/r05_traffic.log 2>&1; tail -2 gpurun_out/r05_traffic.log | cut -c1-200
 [ -f gpurun_out/r05_pmc_traffic.json ] && cp gpurun_out/r05_pmc_traffic.json profiles/r05_pmc_traffic.json
@@ -10,8 +11,8 @@ cp gpurun_out/r05_fwd_enc_TA.json gpurun_out/r05_fwd_enc_TA.txt profiles/ 2>/dev
 timeout -k 5 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 > gpurun_out/r05_final_tests.log
 cat gpurun_out/r05_final_tests.log
 timeout -k 5 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout -k 5 900 python bench.py > gpurun_out/r05_bench_line.json 2> gpurun_out/r05_bench_default.err
-tail -2 gpurun_out/r05_bench_default.err
+timeout -k 5 900 python bench.py --full > $O/r05_bench_line.json 2> $O/r05_bench_default.err
+tail -2 $O/r05_bench_default.err
 SEMIDETR_BENCH_SHARE_GPU=1 SEMIDETR_DIST_BACKEND=gloo timeout -k 5 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --backbone-ms 8 > gpurun_out/r05_bench_line_2ranks_gloo.json 2> gpurun_out/r05_bench_2ranks.err
 tail -1 gpurun_out/r05_bench_line_2ranks_gloo.json | cut -c1-100
 cd /tmp && export TMPDIR=/tmp
@@ -21,9 +22,9 @@ cd $R
 python tools/summarize_prof.py stats gpurun_out/r05_prof_bench > gpurun_out/r05_bench_kernel_stats.txt
 python tools/summarize_prof.py bygrid gpurun_out/r05_prof_bench > gpurun_out/r05_bench_kernel_by_grid.txt
 head -26 gpurun_out/r05_bench_kernel_by_grid.txt
-python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/r05_bench_line.json").read().strip().splitlines()[-1])
+python - "$O" <<'PY'
+import json, sys
+d = json.loads(open(sys.argv[1] + "/r05_bench_line.json").read().strip().splitlines()[-1])
 print({k: round(d[k], 2) for k in ("value", "ms_per_step")}, "frac", round(d["roofline"]["frac"], 4), d["roofline"]["kernel"], d["roofline"]["kernel_symbols"], "traffic", d["roofline"]["traffic"])
 print({k: round(v, 3) for k, v in d["breakdown_ms_per_step"].items()})
 print({k: (round(v["ms_per_step"], 2), round(v["images_per_s"], 1)) for k, v in d["flavours"].items() if isinstance(v, dict)})

@@ -1,9 +1,10 @@
 #!/bin/bash
-mkdir -p gpurun_out
-timeout -k 5 900 python bench.py --steps 10 --warmup 3 > gpurun_out/bench_quick.json 2> gpurun_out/bench_quick.err; tail -3 gpurun_out/bench_quick.err
-python - <<'PY'
-import json
-d=json.loads(open("gpurun_out/bench_quick.json").read().strip().splitlines()[-1])
+O=${BENCH_OUT:-bench_out}      # output directory (relative to the repository root)
+mkdir -p $O
+timeout -k 5 900 python bench.py --full --steps 10 --warmup 3 > $O/bench_quick.json 2> $O/bench_quick.err; tail -3 $O/bench_quick.err
+python - "$O" <<'PY'
+import json, sys
+d=json.loads(open(sys.argv[1] + "/bench_quick.json").read().strip().splitlines()[-1])
 print("value", d["value"], "ms", d["ms_per_step"])
 print("roofline", d["roofline"]["kernel"], d["roofline"]["frac"])
 print("warmup_stage", d.get("warmup_stage"))
