@@ -386,6 +386,47 @@ int semidetr_tal_loss_f32(void *stream, const float *logits, const int64_t *labe
                           int64_t num_rows, int num_classes, float gamma, int input_is_prob, void *workspace,
                           float *loss_sum, float *grad_logits);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cost-GMM double filter of the unsupervised loss (ABI 7, additive): matched costs at the LSAP pairs, a two-component
+ * one-feature Gaussian-mixture threshold over them (one rank or all ranks), then the two pseudo-label index sets.
+ *
+ * Replaces  the per-image loop + concat_all_gather + _fit_gmm + the per-image filter of DinoDetrSSOD.unsup_loss
+ *               detr_ssod/models/dino_detr_ssod.py:243-353, DinoDetrSSOD._fit_gmm :832-890 (sklearn GaussianMixture,
+ *               covariance_type 'diag', weights_init [.5,.5], means_init [min,max], precisions_init [[1],[1]])
+ *
+ * semidetr_gmm_match_costs_f32: cost (match_cost layout of semidetr_match_cost_f32), gt_offsets (B+1,) int32, pair_offsets
+ *   (B+1,) int32 DEVICE (image b's LSAP pairs are rows/cols [pair_offsets[b], pair_offsets[b+1]) of semidetr_lsap_solve);
+ *   num_pairs (host) = pair_offsets[B] <= capacity.  out_seg[k] = cost[rows[k], cols[k]] of problem b, out_count (1,)
+ *   int32 = num_pairs: one segment of the padded buffer semidetr_gmm_fit_f64 reads.
+ * semidetr_gmm_fit_f64: num_segments segments, segment s = values[s * value_stride + j], j < counts[s * count_stride]
+ *   (DEVICE int32, each in [0, capacity]); the fit runs over their concatenation in segment order.  covariance_type must be
+ *   SEMIDETR_GMM_COVARIANCE_DIAG.  One workgroup, fp64, scikit-learn 1.7.2's EM step for step.  out_thr (1,) fp32: 0 for no
+ *   point, the point for one, otherwise the cost of the best-scoring component-0 point (component 1 if component 0 is
+ *   empty; equal scores -> the smaller cost).  out_labels (n,) int32 / out_scores (n,) fp64 (nullable) = predict /
+ *   score_samples in the concatenated order (NaN scores for n < 2).  out_info (4,) int32 = n_iter, converged, error
+ *   (0 ok, 1 a covariance <= 0 -- sklearn raises there --, 2 a count outside [0, capacity]; out_thr is NaN on error), n.
+ * semidetr_gmm_double_filter_f32: per image b (gt rows [gt_offsets[b], gt_offsets[b+1]), at most max_gt <= slot and
+ *   <= 8192 of them): keep_base = {g : gt_scores[g] >= base_thr}, keep_gmm = {cols[k] : seg_costs[k] <= *thr} over the
+ *   image's pairs; boxes (sumG,4) fp32.  Ascending indices, written from b * slot: out_base_* = gt_* at keep_base,
+ *   out_gmm_* = gt_* and out_det_* = det_* at keep_base | keep_gmm; out_counts (2,B) int32 = (|keep_base|, |union|).
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_GMM_COVARIANCE_DIAG 1
+int semidetr_gmm_match_costs_f32(void *stream, const float *cost, const int32_t *gt_offsets, const int32_t *pair_offsets,
+                                 const int64_t *rows, const int64_t *cols, int num_images, int num_query, int num_pairs,
+                                 int capacity, float *out_seg, int32_t *out_count);
+int semidetr_gmm_fit_f64(void *stream, const float *values, int64_t value_stride, const int32_t *counts,
+                         int64_t count_stride, int num_segments, int capacity, int covariance_type, double reg_covar,
+                         double tol, int max_iter, float *out_thr, int32_t *out_labels, double *out_scores,
+                         int32_t *out_info);
+int semidetr_gmm_double_filter_f32(void *stream, const float *seg_costs, const int32_t *pair_offsets, const int64_t *cols,
+                                   const float *thr, const float *gt_bboxes, const int64_t *gt_labels,
+                                   const float *gt_scores, const float *det_bboxes, const int64_t *det_labels,
+                                   const float *det_scores, const int32_t *gt_offsets, int num_images, int max_gt,
+                                   float base_thr, int slot, float *out_base_boxes, int64_t *out_base_labels,
+                                   float *out_base_scores, float *out_gmm_boxes, int64_t *out_gmm_labels,
+                                   float *out_gmm_scores, float *out_det_boxes, int64_t *out_det_labels,
+                                   float *out_det_scores, int32_t *out_counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,10 +22,13 @@ from .matcher import (AssignResult, BBoxL1Cost, FocalLossCost, HungarianAssigner
 from .losses import TaskAlignedFocalLoss, task_aligned_focal_loss  # noqa: E402,F401
 from .mean_teacher import MeanTeacher, ema_momentum, ema_update_, ema_update_flat_  # noqa: E402,F401
 from .targets import TargetAssigner, get_targets, get_targets_layers  # noqa: E402,F401
+from .gmm_filter import (GmmFilterResult, PendingGmmFilter, fit_gmm, fit_gmm_threshold,  # noqa: E402,F401
+                         fit_gmm_threshold_segments, unsup_gmm_filter)
 from .pseudo_label import (filter_pseudo_labels, get_bboxes_for_pseudo_label, teacher_pseudo_labels,  # noqa: E402,F401
                            transform_bboxes)
 
 __all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttn", "HungarianAssigner", "FocalLossCost", "BBoxL1Cost",
            "IoUCost", "AssignResult", "O2MAssigner", "O2MAssignResult", "TaskAlignedFocalLoss", "task_aligned_focal_loss", "linear_sum_assignment", "MeanTeacher", "ema_momentum", "ema_update_",
            "ema_update_flat_", "filter_pseudo_labels", "get_bboxes_for_pseudo_label", "teacher_pseudo_labels",
-           "transform_bboxes", "TargetAssigner", "get_targets", "get_targets_layers"]
+           "transform_bboxes", "TargetAssigner", "get_targets", "get_targets_layers", "fit_gmm", "fit_gmm_threshold",
+           "fit_gmm_threshold_segments", "unsup_gmm_filter", "GmmFilterResult", "PendingGmmFilter"]

@@ -58,6 +58,10 @@ SIGNATURES = {
     "semidetr_tal_loss_workspace_bytes": (ctypes.c_size_t, []),
     "semidetr_tal_loss_f32": (c_int, [c_void_p] * 4 + [c_int64, c_int, ctypes.c_float, c_int] + [c_void_p] * 3),
     "semidetr_transform_bboxes_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3),
+    "semidetr_gmm_match_costs_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 2),
+    "semidetr_gmm_fit_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 3 + [c_double, c_double, c_int]
+                             + [c_void_p] * 4),
+    "semidetr_gmm_double_filter_f32": (c_int, [c_void_p] * 12 + [c_int, c_int, ctypes.c_float, c_int] + [c_void_p] * 10),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so
