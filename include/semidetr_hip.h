@@ -427,6 +427,70 @@ int semidetr_gmm_double_filter_f32(void *stream, const float *seg_costs, const i
                                    float *out_gmm_scores, float *out_det_boxes, int64_t *out_det_labels,
                                    float *out_det_scores, int32_t *out_counts);
 
+/* ---------------------------------------------------------------------------------------------
+ * Set-prediction losses of the SSOD head (ABI 7, additive): sigmoid focal (task-aligned focal in warm-up), L1 on cxcywh
+ * (all / xy / hw) and GIoU on image-scale xyxy, for every (segment, layer) of one loss() call, deterministic sums.
+ *
+ * Replaces  DINODETRSSODHead.loss / loss_single / loss_single_dn / get_targets_dn / _get_target_single_dn
+ *               detr_od/models/dense_heads/dino_detr_ssod_head.py:508-985, with mmdet FocalLoss (py_sigmoid_focal_loss),
+ *               L1Loss, GIoULoss + bbox_overlaps(mode='giou', is_aligned=True)
+ *
+ * A segment is (num_layers, num_images, num_query, num_classes) of logits (class dimension unit stride, other strides in
+ * elements: layer, image, query) and boxes (cxcywh, coordinate dimension unit stride; NULL: no box terms) plus its targets:
+ *   MATCHED / WARMUP: labels (nl*B, Q) int64 in [0, C] (C = background), label_weights (nl*B, Q) (NULL = 1; MATCHED only),
+ *     bbox_targets / bbox_weights (nl*B, Q, 4), metrics (nl*B, Q) normalised alignment metrics (WARMUP only; the
+ *     classification term is then the task-aligned focal loss of semidetr_tal_loss_f32 on the logits, box terms cover the
+ *     rows with label < C only);
+ *   DN: built in the kernel from gt_offsets (B+1,) int32, gt_boxes (sumG, 4) xyxy image scale, gt_labels (sumG,) int64,
+ *     single_pad, dn_groups (num_query = single_pad * dn_groups, every G_b <= single_pad): row q of image b is positive iff
+ *     q % single_pad < G_b, label_weights = 1 if G_b > 0 else 0 (_get_target_single_dn).
+ *   img_wh (B, 2) fp32 (w, h) of each image: the GIoU scale factors (and the dn targets' normalisation).
+ * Per (segment, layer) t (segments in table order, layers ascending):
+ *   stats (T, 10) fp64 = cls sum, L1 sum, L1 xy, L1 hw, GIoU sum (weight mean_k w_k), rows with label < C, rows with
+ *     sum_k w_k > 0, rows with any w_k > 0, sum over rows with label < C of w_0, sum of metrics;
+ *   norms (T, 2) fp32 = normaliser inputs before any cross-rank mean (cls: num_pos + num_neg * bg_cls_weight, or the
+ *     metric sum in WARMUP; reg: rows with sum w > 0 (MATCHED), num_pos (DN), sum w_0 of positives (WARMUP));
+ *   losses / scales (T, 5) fp32 in the order cls, bbox (L1), iou, bbox_xy, bbox_hw: scale = loss_weight / max(norm, 1)
+ *     (0 for iou when no bbox weight is > 0), loss = sum * scale.
+ * forward: the two launches; losses / scales NULL -> not finalized (several ranks: all-reduce-mean the norms, then
+ *   finalize, which takes the reduced reg normaliser always and the reduced cls one for WARMUP or sync_cls).
+ * backward: grad_logits (nl, B, Q, C) / grad_boxes (nl, B, Q, 4) dense fp32 of each segment (NULL: not wanted) =
+ *   sum_k scales[t, k] * grad_out[t, k] * d sum_k / d input (scales NULL = 1); grad_out (T, 5) fp32.
+ * Limits: <= 3 segments, <= 64 (segment, layer) pairs, rows * C < 2^31 per segment.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_SET_LOSS_MATCHED 0
+#define SEMIDETR_SET_LOSS_DN 1
+#define SEMIDETR_SET_LOSS_WARMUP 2
+#define SEMIDETR_SET_LOSS_MAX_SEGMENTS 3
+#define SEMIDETR_SET_LOSS_MAX_LAYERS 64
+#define SEMIDETR_SET_LOSS_NUM_STATS 10
+#define SEMIDETR_SET_LOSS_NUM_TERMS 5
+typedef struct semidetr_set_loss_segment {
+    int kind, num_layers, num_images, num_query, num_classes;
+    const float *logits;
+    int64_t logit_stride[3];
+    const float *boxes;
+    int64_t box_stride[3];
+    const int64_t *labels;
+    const float *label_weights, *bbox_targets, *bbox_weights, *metrics;
+    const int32_t *gt_offsets;
+    const float *gt_boxes;
+    const int64_t *gt_labels;
+    int single_pad, dn_groups;
+    const float *img_wh;
+    float alpha, gamma, cls_weight, l1_weight, iou_weight, iou_eps, bg_cls_weight;
+    int sync_cls;
+    float *grad_logits, *grad_boxes;
+} semidetr_set_loss_segment;
+int64_t semidetr_set_loss_workspace_bytes(const semidetr_set_loss_segment *segs, int num_segments);
+int semidetr_set_loss_forward_f32(void *stream, const semidetr_set_loss_segment *segs, int num_segments, void *workspace,
+                                  int64_t workspace_bytes, double *stats, float *norms, float *losses, float *scales);
+int semidetr_set_loss_finalize_f32(void *stream, const semidetr_set_loss_segment *segs, int num_segments,
+                                   const double *stats, const float *norms_local, const float *norms_reduced,
+                                   float *losses, float *scales);
+int semidetr_set_loss_backward_f32(void *stream, const semidetr_set_loss_segment *segs, int num_segments,
+                                   const float *scales, const float *grad_out);
+
 #ifdef __cplusplus
 }
 #endif

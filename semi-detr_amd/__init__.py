@@ -24,6 +24,7 @@ from .mean_teacher import MeanTeacher, ema_momentum, ema_update_, ema_update_fla
 from .targets import TargetAssigner, get_targets, get_targets_layers  # noqa: E402,F401
 from .gmm_filter import (GmmFilterResult, PendingGmmFilter, fit_gmm, fit_gmm_threshold,  # noqa: E402,F401
                          fit_gmm_threshold_segments, unsup_gmm_filter)
+from .set_loss import FocalLoss, SetLossSegment, loss_set, set_losses  # noqa: E402,F401
 from .pseudo_label import (filter_pseudo_labels, get_bboxes_for_pseudo_label, teacher_pseudo_labels,  # noqa: E402,F401
                            transform_bboxes)
 
@@ -31,4 +32,5 @@ __all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttn", 
            "IoUCost", "AssignResult", "O2MAssigner", "O2MAssignResult", "TaskAlignedFocalLoss", "task_aligned_focal_loss", "linear_sum_assignment", "MeanTeacher", "ema_momentum", "ema_update_",
            "ema_update_flat_", "filter_pseudo_labels", "get_bboxes_for_pseudo_label", "teacher_pseudo_labels",
            "transform_bboxes", "TargetAssigner", "get_targets", "get_targets_layers", "fit_gmm", "fit_gmm_threshold",
-           "fit_gmm_threshold_segments", "unsup_gmm_filter", "GmmFilterResult", "PendingGmmFilter"]
+           "fit_gmm_threshold_segments", "unsup_gmm_filter", "GmmFilterResult", "PendingGmmFilter",
+           "FocalLoss", "SetLossSegment", "loss_set", "set_losses"]

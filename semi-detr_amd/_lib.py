@@ -62,6 +62,11 @@ SIGNATURES = {
     "semidetr_gmm_fit_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 3 + [c_double, c_double, c_int]
                              + [c_void_p] * 4),
     "semidetr_gmm_double_filter_f32": (c_int, [c_void_p] * 12 + [c_int, c_int, ctypes.c_float, c_int] + [c_void_p] * 10),
+    # the segment table (semidetr_set_loss_segment[], set_loss._Segment) is passed as a host pointer
+    "semidetr_set_loss_workspace_bytes": (c_int64, [c_void_p, c_int]),
+    "semidetr_set_loss_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64] + [c_void_p] * 4),
+    "semidetr_set_loss_finalize_f32": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 5),
+    "semidetr_set_loss_backward_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so

@@ -45,3 +45,16 @@ def register_all(force=True):
     except ImportError:
         skipped.append("FlatDDP")
     return done, skipped
+
+
+def register_losses(force=True):
+    """``FocalLoss`` under mmdet's ``LOSSES`` (configs name it as ``loss_cls2``, dino_detr_ssod_r50_coco_120k.py:36-41):
+    the mmcv-full op it calls on GPU tensors is not part of this stack.  Separate from ``register_all`` so that callers
+    opt in.  Returns (registered, skipped) names."""
+    try:
+        from mmdet.models.builder import LOSSES
+        from .set_loss import FocalLoss
+        LOSSES.register_module(name="FocalLoss", force=force, module=FocalLoss)
+        return ["FocalLoss"], []
+    except ImportError:
+        return [], ["FocalLoss"]
