@@ -491,6 +491,86 @@ int semidetr_set_loss_finalize_f32(void *stream, const semidetr_set_loss_segment
 int semidetr_set_loss_backward_f32(void *stream, const semidetr_set_loss_segment *segs, int num_segments,
                                    const float *scales, const float *grad_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * De-noising and consistency queries (ABI 7, additive): the producer of the `dn_meta` that the DN segment above consumes.
+ *
+ * Replaces  prepare_for_cdn / prepare_for_cdn_plus   detr_od/models/dense_heads/dn_components.py:6-125,128-274
+ *           DinoDetrSSOD.prepare_unsup_cdn           detr_ssod/models/dino_detr_ssod.py:484-760
+ *           (without RoIAlign and the projector, which stay calls of the caller)
+ *
+ * Every size follows from the LENGTHS of the per-image lists, which the caller has on the host, so the tables below are
+ * host data passed by value and nothing is read back.  A layout places N = offsets[num_images] list rows into
+ * (num_images, groups * single_pad) slots: slot s = i * single_pad + j of image b holds row k = i * N + offsets[b] + j iff
+ * j < offsets[b + 1] - offsets[b]; the other slots are padding.  K = groups * N rows exist in all.
+ *
+ * semidetr_dn_build_f32 -- one launch, three jobs on disjoint workgroups, every element of every output written:
+ *   (a) the contrastive de-noising queries (dn.groups = 2 * num_dn_group; even i = positive, odd i = negative).  Image b's
+ *       ground truths are labels[b] (src_counts[b],) int64 and boxes[b] (src_counts[b] rows of box_stride floats, normalised
+ *       cx,cy,w,h first).  An image with src_counts[b] == 0 whose layout count is 1 gets the reference's stand-in: box
+ *       (.5,.5,.5,.5), label (int)(image_noise[b] * 80), pad_mask 1.  noise (K, 10) uniform in [0, 1):
+ *       column 0 = p (label flipped iff p < label_noise_threshold = label_noise_ratio / 2; <= 0: never),
+ *       1 -> new label min((int)(u * num_classes), num_classes - 1) in fp32, 2..5 -> sign (+1 iff u >= .5) of x1,y1,x2,y2,
+ *       6..9 = rand_part of x1,y1,x2,y2 (+1 for negatives).  box_noise_scale <= 0: boxes pass unchanged.
+ *       query_label (B, pad, hidden) = rows of label_weight (num_embeddings, hidden) at the noised labels (a label outside
+ *       the table gives a NaN row), 0 in padding; query_bbox (B, pad, 4) = inverse_sigmoid(noised box, eps 1e-5), 0 in
+ *       padding; known_bid / map_known_indice / noised_labels (K,) int64; pad_mask (B, pad) int64 or NULL.
+ *   (b) cons_rows != NULL: cons_label (B, cons.groups * cons.single_pad, hidden) = cons_rows (K1, hidden) scattered by `cons`.
+ *   (c) attn_mask != NULL: (tgt, tgt) bytes, tgt = pad1 + pad + num_queries with pad1 = cons.groups * cons.single_pad
+ *       (cons.groups == 0: no consistency part): mask[r][c] = c < pad1 + pad && (r >= pad1 + pad || group(r) != group(c)),
+ *       groups = the cons.groups blocks of cons.single_pad followed by the num_dn_group blocks of 2 * dn.single_pad.
+ *       attn_mask must be 16-byte aligned.
+ * semidetr_dn_consistency_f32 -- one launch: image b's pseudo boxes pseudo_boxes[b] (src_counts[b] rows of pseudo_stride
+ *   floats, x1,y1,x2,y2 pixels of the target view, tgt_wh[b] = (w, h)) -> query_bbox (B, pad1, 4) = inverse_sigmoid of the
+ *   normalised, clamped cx,cy,w,h (0 in padding), known_bid (K1,) fp32, map_known_indice (K1,) int64; rois (K1, 5) or NULL
+ *   = (image, det_boxes[b] row); loss_weights (K1,) or NULL = loss_weight.  An image without boxes has layout count 1:
+ *   its box is (w/4, h/4, 3w/4, 3h/4) of tgt_wh (rois: of src_wh) and its weight 0.
+ * semidetr_dn_label_backward_f32 -- grad_weight (num_embeddings, hidden), every element written: row e = sum over k with
+ *   noised_labels[k] == e, in ascending k, of grad_query_label[known_bid[k], map_known_indice[k], :].  No atomics: one
+ *   workgroup per row, so the result is bitwise reproducible.
+ * semidetr_dn_gather_rows_f32 -- grad_rows (K1, hidden) = grad_label (B, pad1, hidden) at the layout's slots (backward of (b)).
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_DN_MAX_IMAGES 64
+#define SEMIDETR_DN_NOISE_COLS 10
+typedef struct semidetr_dn_layout {
+    int num_images, single_pad, groups;
+    int32_t offsets[SEMIDETR_DN_MAX_IMAGES + 1];   /* HOST values */
+} semidetr_dn_layout;
+typedef struct semidetr_dn_build {
+    semidetr_dn_layout dn, cons;
+    int32_t src_counts[SEMIDETR_DN_MAX_IMAGES];
+    const int64_t *labels[SEMIDETR_DN_MAX_IMAGES];
+    const float *boxes[SEMIDETR_DN_MAX_IMAGES];
+    int box_stride, num_known;                      /* num_known = K = dn.groups * dn.offsets[num_images] */
+    const float *label_weight;
+    int num_embeddings, hidden_dim, num_classes, num_queries;
+    const float *noise, *image_noise;
+    float label_noise_threshold, box_noise_scale;
+    float *query_label, *query_bbox;
+    int64_t *known_bid, *map_known_indice, *noised_labels, *pad_mask;
+    const float *cons_rows;
+    float *cons_label;
+    unsigned char *attn_mask;
+} semidetr_dn_build;
+typedef struct semidetr_dn_consistency {
+    semidetr_dn_layout cons;
+    int32_t src_counts[SEMIDETR_DN_MAX_IMAGES];
+    const float *pseudo_boxes[SEMIDETR_DN_MAX_IMAGES];
+    const float *det_boxes[SEMIDETR_DN_MAX_IMAGES];
+    int pseudo_stride, det_stride, num_known;       /* num_known = K1 = cons.groups * cons.offsets[num_images] */
+    float tgt_wh[SEMIDETR_DN_MAX_IMAGES][2], src_wh[SEMIDETR_DN_MAX_IMAGES][2];
+    float *query_bbox, *known_bid;
+    int64_t *map_known_indice;
+    float *loss_weights, *rois;
+    float loss_weight;                              /* written for an image that has boxes (1, or 0 past the warm-up) */
+} semidetr_dn_consistency;
+int semidetr_dn_build_f32(void *stream, const semidetr_dn_build *params /* host */);
+int semidetr_dn_consistency_f32(void *stream, const semidetr_dn_consistency *params /* host */);
+int semidetr_dn_label_backward_f32(void *stream, const float *grad_query_label, const int64_t *known_bid,
+                                   const int64_t *map_known_indice, const int64_t *noised_labels, int num_known,
+                                   int num_images, int pad_size, int hidden_dim, int num_embeddings, float *grad_weight);
+int semidetr_dn_gather_rows_f32(void *stream, const semidetr_dn_layout *layout /* host */, const float *grad_label,
+                                int hidden_dim, float *grad_rows);
+
 #ifdef __cplusplus
 }
 #endif

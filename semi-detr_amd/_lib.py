@@ -67,6 +67,11 @@ SIGNATURES = {
     "semidetr_set_loss_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64] + [c_void_p] * 4),
     "semidetr_set_loss_finalize_f32": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 5),
     "semidetr_set_loss_backward_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    # the parameter blocks (semidetr_dn_build / _consistency / _layout, dn_query._Build ...) are passed as host pointers
+    "semidetr_dn_build_f32": (c_int, [c_void_p, c_void_p]),
+    "semidetr_dn_consistency_f32": (c_int, [c_void_p, c_void_p]),
+    "semidetr_dn_label_backward_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
+    "semidetr_dn_gather_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so

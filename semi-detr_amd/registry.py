@@ -58,3 +58,31 @@ def register_losses(force=True):
         return ["FocalLoss"], []
     except ImportError:
         return [], ["FocalLoss"]
+
+
+def bind_dn_queries():
+    """Rebind the reference's query builders to ``semi_detr_amd.dn_query`` where ``detr_od`` / ``detr_ssod`` are importable:
+    ``prepare_for_cdn`` as the supervised head's module global (dino_detr_head.py:1032), ``prepare_for_cdn_plus`` as the SSOD
+    head's (dino_detr_ssod_head.py:1263; both call them by bare name, so the importing module's attribute is what counts,
+    and dn_components' own is replaced too) and ``DinoDetrSSOD.prepare_unsup_cdn``.  Returns (bound, skipped) names."""
+    import importlib
+
+    from . import dn_query
+    done, skipped = [], []
+    for mod, name in (("detr_od.models.dense_heads.dino_detr_head", "prepare_for_cdn"),
+                      ("detr_od.models.dense_heads.dino_detr_ssod_head", "prepare_for_cdn_plus")):
+        try:
+            m = importlib.import_module(mod)
+            setattr(m, name, getattr(dn_query, name))
+            comp = importlib.import_module("detr_od.models.dense_heads.dn_components")
+            setattr(comp, name, getattr(dn_query, name))
+            done.append(name)
+        except ImportError:
+            skipped.append(name)
+    try:
+        m = importlib.import_module("detr_ssod.models.dino_detr_ssod")
+        m.DinoDetrSSOD.prepare_unsup_cdn = dn_query.prepare_unsup_cdn
+        done.append("DinoDetrSSOD.prepare_unsup_cdn")
+    except ImportError:
+        skipped.append("DinoDetrSSOD.prepare_unsup_cdn")
+    return done, skipped
