@@ -571,6 +571,54 @@ int semidetr_dn_label_backward_f32(void *stream, const float *grad_query_label, 
 int semidetr_dn_gather_rows_f32(void *stream, const semidetr_dn_layout *layout /* host */, const float *grad_label,
                                 int hidden_dim, float *grad_rows);
 
+/* ---------------------------------------------------------------------------------------------
+ * Two-stage query selection (ABI 7, additive): what DINOTransformer.forward runs between the encoder and the decoder.
+ *
+ * Replaces  gen_encoder_output_proposals             detr_od/models/utils/transformer.py:525-575 (learnedwh is None)
+ *           max(-1) + torch.topk + the three gathers transformer.py:1325-1334
+ *           refpoint_embed_undetach.sigmoid()        transformer.py:1398
+ *           (the enc_output / enc_output_norm / head GEMMs between them stay calls of the caller)
+ *
+ * fp32, on `stream`, no host synchronisation, nothing read back; every element of every output is written (no memset).
+ *
+ * semidetr_qsel_proposals_f32 -- one launch.  memory (N, S, D), padding_mask (N, S) bytes (non-zero = padded), the levels
+ *   as (num_levels, 2) int64 (H, W) rows either on the host (validated: they must hold S tokens) or on the device (exactly one
+ *   of the two pointers; a device table that does not fit S yields masked tokens, never an out-of-bounds access).  For token
+ *   (y, x) of level l:  p = ((x + .5) / valid_W, (y + .5) / valid_H, .05 * 2^l, .05 * 2^l) with valid_H / valid_W the number of
+ *   unmasked entries in column 0 / row 0 of the level (IEEE correctly rounded fp32 quotients),
+ *   valid = all(p > 0.01f & p < 0.99f) & !mask;  output_proposals (N, S, 4) = valid ? log(p / (1 - p)) : +inf;
+ *   output_memory (N, S, D) = valid ? memory : 0;  valid (N, S) bytes.
+ * semidetr_qsel_proposals_backward_f32 -- one launch: grad_memory = valid ? grad_output_memory : 0.
+ * semidetr_qsel_topk_f32 -- two launches (class max over all CUs; one workgroup per image selects).  logits (N, S, C):
+ *   key = max over C (NaN propagates and ranks above +inf, -0 == +0);  indices (N, k) int64 = the k largest keys sorted by
+ *   (key descending, token index ascending), a total order;  inverse (N, S) int32 = slot of the token or -1.
+ *   workspace: semidetr_qsel_topk_workspace_bytes(N, S) bytes.  k <= min(S, SEMIDETR_QSEL_MAX_K).
+ * semidetr_qsel_gather_f32 -- one launch: refpoint (N, k, 4) = rows of coord (N, S, 4), init_box = sigmoid(rows of
+ *   proposals), tgt (N, k, D) = rows of memory (N, S, D), ref_enc = sigmoid(refpoint).  An index outside [0, S) gives NaN.
+ * semidetr_qsel_gather_backward_f32 -- one launch, no atomics, bitwise reproducible: through `inverse`,
+ *   grad_coord (N, S, 4) = grad_refpoint + grad_ref_enc * ref_enc * (1 - ref_enc) of the token's slot, grad_memory (N, S, D)
+ *   = grad_tgt of the slot, zero for unselected tokens.  Any of the three incoming gradients may be NULL (= zero), and one
+ *   of the two outputs.
+ * Limits (SEMIDETR_E_TOOLARGE beyond them): N * S < 2^31, N <= 65535, D <= 65536, and for the two gather entry points
+ *   N * k < 2^24.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_QSEL_MAX_LEVELS 8
+#define SEMIDETR_QSEL_MAX_K 4096
+int semidetr_qsel_proposals_f32(void *stream, const float *memory, const unsigned char *padding_mask,
+                                const int64_t *spatial_shapes_host, const int64_t *spatial_shapes_dev, int num_levels, int N,
+                                int S, int D, float *output_memory, float *output_proposals, unsigned char *valid);
+int semidetr_qsel_proposals_backward_f32(void *stream, const float *grad_output_memory, const unsigned char *valid, int N, int S,
+                                         int D, float *grad_memory);
+size_t semidetr_qsel_topk_workspace_bytes(int N, int S);
+int semidetr_qsel_topk_f32(void *stream, const float *logits, int N, int S, int C, int k, void *workspace,
+                           size_t workspace_bytes, int64_t *indices, int32_t *inverse);
+int semidetr_qsel_gather_f32(void *stream, const int64_t *indices, const float *coord, const float *proposals,
+                             const float *memory, int N, int S, int k, int D, float *refpoint, float *init_box, float *tgt,
+                             float *ref_enc);
+int semidetr_qsel_gather_backward_f32(void *stream, const int32_t *inverse, const float *grad_refpoint, const float *grad_tgt,
+                                      const float *grad_ref_enc, const float *ref_enc, int N, int S, int k, int D,
+                                      float *grad_coord, float *grad_memory);
+
 #ifdef __cplusplus
 }
 #endif

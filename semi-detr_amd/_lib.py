@@ -72,6 +72,13 @@ SIGNATURES = {
     "semidetr_dn_consistency_f32": (c_int, [c_void_p, c_void_p]),
     "semidetr_dn_label_backward_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
     "semidetr_dn_gather_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    # two-stage query selection (query_select.py)
+    "semidetr_qsel_proposals_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 3),
+    "semidetr_qsel_proposals_backward_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    "semidetr_qsel_topk_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),
+    "semidetr_qsel_topk_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
+    "semidetr_qsel_gather_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 4),
+    "semidetr_qsel_gather_backward_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 2),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so

@@ -86,3 +86,21 @@ def bind_dn_queries():
     except ImportError:
         skipped.append("DinoDetrSSOD.prepare_unsup_cdn")
     return done, skipped
+
+
+def bind_query_select():
+    """Bind the two-stage query selection to ``semi_detr_amd.query_select`` where ``detr_od`` is importable:
+    ``gen_encoder_output_proposals`` as the module global of detr_od.models.utils.transformer (``DINOTransformer.forward`` calls
+    it by bare name, transformer.py:1318) and ``DINOTransformer.two_stage_queries`` as a helper method (INTEGRATION.md shows the
+    call that replaces transformer.py:1315-1346 and 1394-1398).  Returns (bound, skipped) names."""
+    import importlib
+
+    from . import query_select
+    names = ["gen_encoder_output_proposals", "DINOTransformer.two_stage_queries"]
+    try:
+        m = importlib.import_module("detr_od.models.utils.transformer")
+    except ImportError:
+        return [], names
+    m.gen_encoder_output_proposals = query_select.gen_encoder_output_proposals
+    m.DINOTransformer.two_stage_queries = query_select.two_stage_queries
+    return names, []
