@@ -3,8 +3,11 @@
 There is NO fallback: if the shared library is missing or a call fails, an exception is raised.  The
 library is built in-tree by ``__graft_entry__.build()`` / ``make -C semi-detr_amd/csrc``.
 """
+import contextlib
 import ctypes
 import os
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SEMIDETR_EXPERIMENTS=1 (tests that force kernel variants, tools/, bench.py's HBM-peak probe) selects the experiments
@@ -120,8 +123,76 @@ def check(rc, what):
 
 
 def current_stream_ptr():
-    import torch
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# ---------------------------------------------------------------------------------------------
+# the one call path of the host mirrors
+# ---------------------------------------------------------------------------------------------
+_NO_GUARD = contextlib.nullcontext()
+_Tensor = torch.Tensor              # bound once: ptr_args tests every argument of every launch
+_functions = {}                     # name -> (library handle, function): looked up and checked once per handle
+
+
+def device_guard(dev):
+    """Device guard only where ``dev`` is not the current device (entering ``torch.cuda.device`` costs more than a launch).
+    A ``dev`` without an index is the current device."""
+    if dev.index is None or dev.index == torch.cuda.current_device():
+        return _NO_GUARD
+    return torch.cuda.device(dev)
+
+
+def ptr_args(args):
+    """Arguments of a C-ABI call: a tensor becomes its data pointer, ``None`` stays ``None`` (NULL for a ``c_void_p``), anything
+    else (Python numbers, ctypes instances, ``ctypes.byref(...)``, ctypes arrays) is left to the argtypes of ``SIGNATURES``."""
+    return [c_void_p(a.data_ptr()) if isinstance(a, _Tensor) else a for a in args]
+
+
+def _function(name):
+    hit = _functions.get(name)
+    if hit is not None and hit[0] is _lib:
+        return hit[1]
+    if name not in SIGNATURES and not (EXPERIMENTS and name in EXPERIMENT_SIGNATURES):
+        raise AttributeError(f"{name} is not a function of the C ABI (_lib.SIGNATURES)")
+    fn = getattr(lib(), name)
+    _functions[name] = (_lib, fn)
+    return fn
+
+
+def calls(dev, *launches):
+    """Launches back to back, each a ``(name, *args)``: ``name(stream, *args)`` on the current stream of ``dev`` with ``dev``
+    current, under one guard decision and one stream lookup.  Every name is resolved before the first launch; a non-zero status
+    raises (``check``) before the next one.  Every entry point that launches takes ``void *stream`` first; the size queries are
+    plain ``lib().f(...)`` calls."""
+    fns = [_function(launch[0]) for launch in launches]
+    with device_guard(dev):
+        stream = c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for fn, launch in zip(fns, launches):
+            rc = fn(stream, *ptr_args(launch[1:]))
+            if rc:
+                check(rc, launch[0])
+
+
+def call(name, dev, *args):
+    """One launch: ``calls(dev, (name, *args))``."""
+    calls(dev, (name,) + args)
+
+
+def small_to_device(values, dtype, dev):
+    """Small host list -> device tensor without a stream synchronisation (pinned staging + async copy); a plain
+    ``torch.tensor(list, device=...)`` is a blocking copy that drains the stream on every call."""
+    host = torch.tensor(values, dtype=dtype)
+    if dev.type == "cuda":
+        return host.pin_memory().to(dev, non_blocking=True)
+    return host.to(dev)
+
+
+def offsets(counts, dev):
+    """Exclusive prefix sum of ``counts`` as (host list, int32 device tensor), one entry more than ``counts``."""
+    offs = [0]
+    for c in counts:
+        offs.append(offs[-1] + int(c))
+    return offs, small_to_device(offs, torch.int32, dev)
 
 
 FORWARD_POLICIES = {"adaptive": 0, "patch": 1, "window": 2}

@@ -142,8 +142,7 @@ class _DnBuildFn(torch.autograd.Function):
         p.known_bid, p.map_known_indice, p.noised_labels = ints[0].data_ptr(), ints[1].data_ptr(), ints[2].data_ptr()
         p.pad_mask = pad_mask.data_ptr() if pad_mask is not None else None
         p.attn_mask = mask.data_ptr()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().semidetr_dn_build_f32(_lib.current_stream_ptr(), ctypes.byref(p)), "semidetr_dn_build_f32")
+        _lib.call("semidetr_dn_build_f32", dev, ctypes.byref(p))
         ctx.st = dict(B=B, pad2=pad2, H=H, K=K, E=w.shape[0], cons=st["cons"], w_dtype=weight.dtype,
                       rows_dtype=None if cons_rows is None else cons_rows.dtype)
         ctx.save_for_backward(ints)
@@ -158,24 +157,18 @@ class _DnBuildFn(torch.autograd.Function):
         (ints,) = ctx.saved_tensors
         st = ctx.st
         gw = grows = None
-        lib = _lib.lib()
-        P = ctypes.c_void_p
-        with torch.cuda.device(ints.device):
-            if ctx.needs_input_grad[0] and g_label is not None:
-                g = g_label.float().contiguous()
-                gw = torch.empty((st["E"], st["H"]), dtype=torch.float32, device=g.device)
-                _lib.check(lib.semidetr_dn_label_backward_f32(_lib.current_stream_ptr(), P(g.data_ptr()), P(ints[0].data_ptr()),
-                                                              P(ints[1].data_ptr()), P(ints[2].data_ptr()), st["K"], st["B"],
-                                                              st["pad2"], st["H"], st["E"], P(gw.data_ptr())),
-                           "semidetr_dn_label_backward_f32")
-                gw = gw.to(st["w_dtype"])
-            if ctx.needs_input_grad[1] and g_cons is not None:
-                g = g_cons.float().contiguous()
-                cons = st["cons"]
-                grows = torch.empty((cons.groups * cons.offsets[cons.num_images], st["H"]), dtype=torch.float32, device=g.device)
-                _lib.check(lib.semidetr_dn_gather_rows_f32(_lib.current_stream_ptr(), ctypes.byref(cons), P(g.data_ptr()),
-                                                           st["H"], P(grows.data_ptr())), "semidetr_dn_gather_rows_f32")
-                grows = grows.to(st["rows_dtype"])
+        if ctx.needs_input_grad[0] and g_label is not None:
+            g = g_label.float().contiguous()
+            gw = torch.empty((st["E"], st["H"]), dtype=torch.float32, device=g.device)
+            _lib.call("semidetr_dn_label_backward_f32", ints.device, g, ints[0], ints[1], ints[2], st["K"], st["B"], st["pad2"],
+                      st["H"], st["E"], gw)
+            gw = gw.to(st["w_dtype"])
+        if ctx.needs_input_grad[1] and g_cons is not None:
+            g = g_cons.float().contiguous()
+            cons = st["cons"]
+            grows = torch.empty((cons.groups * cons.offsets[cons.num_images], st["H"]), dtype=torch.float32, device=g.device)
+            _lib.call("semidetr_dn_gather_rows_f32", ints.device, ctypes.byref(cons), g, st["H"], grows)
+            grows = grows.to(st["rows_dtype"])
         return gw, grows, None
 
 
@@ -307,9 +300,7 @@ def consistency_queries(pseudo_bboxes, det_bboxes, tgt_shapes, src_shapes, loss_
     p.loss_weights = lw.data_ptr() if lw is not None else None
     p.rois = rois.data_ptr() if rois is not None else None
     p.loss_weight = float(loss_weight)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().semidetr_dn_consistency_f32(_lib.current_stream_ptr(), ctypes.byref(p)),
-                   "semidetr_dn_consistency_f32")
+    _lib.call("semidetr_dn_consistency_f32", dev, ctypes.byref(p))
     return dict(query_bbox=q_bbox, known_bid=bid, map_known_indice=mp, loss_weights=lw, rois=rois, layout=lay, pad=pad1,
                 single_pad=single_pad)
 

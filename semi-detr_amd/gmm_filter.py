@@ -12,18 +12,13 @@
 Ties in the threshold pick go to the smaller cost (the reference sorts ascending and takes ``topk``'s first maximum).
 """
 import collections
-import ctypes
 
 import torch
 
 from . import _lib
-from .matcher import _to_device_async, lsap_batch, match_cost_batch
+from .matcher import lsap_batch, match_cost_batch
 
 COVARIANCE_DIAG = 1                 # SEMIDETR_GMM_COVARIANCE_DIAG
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 def _check_covariance(covariance_type):
@@ -41,13 +36,9 @@ def _fit(values, value_stride, counts, count_stride, world, capacity, n_max, reg
     want = details and n_max > 0            # the kernel writes n values through these: never hand it an empty tensor's pointer
     if int(max_iter) < 1:
         raise ValueError(f"max_iter must be >= 1, got {max_iter}")
-    with torch.cuda.device(dev):
-        rc = _lib.lib().semidetr_gmm_fit_f64(_lib.current_stream_ptr(), _p(values), int(value_stride), _p(counts),
-                                             int(count_stride), int(world), int(capacity), COVARIANCE_DIAG,
-                                             float(reg_covar), float(tol), int(max_iter), _p(thr), _p(labels if want else None),
-                                             _p(scores if want else None),
-                                             _p(info))
-    _lib.check(rc, "semidetr_gmm_fit_f64")
+    _lib.call("semidetr_gmm_fit_f64", dev, values, int(value_stride), counts, int(count_stride), int(world), int(capacity),
+              COVARIANCE_DIAG, float(reg_covar), float(tol), int(max_iter), thr, labels if want else None,
+              scores if want else None, info)
     if not details:
         return thr
     return thr, dict(labels=labels, scores=scores, n_iter=info[0], converged=info[1] != 0, error=info[2], info=info)
@@ -64,7 +55,7 @@ def fit_gmm_threshold(costs, covariance_type="diag", reg_covar=1e-5, tol=1e-3, m
         raise RuntimeError("fit_gmm_threshold: costs must live on the GPU (no CPU fallback)")
     x = costs.detach().reshape(-1).to(torch.float32).contiguous()
     n = x.numel()
-    count = _to_device_async([n], torch.int32, x.device)
+    count = _lib.small_to_device([n], torch.int32, x.device)
     return _fit(x, n, count, 1, 1, n, n, reg_covar, tol, max_iter, return_details)
 
 
@@ -228,7 +219,7 @@ def unsup_gmm_filter(cls_scores, bbox_preds, gt_bboxes_list, gt_labels_list, gt_
     det_b = _cat(det_bboxes_list, 4, torch.float32, dev)
     det_l = _cat(det_labels_list, 0, torch.int64, dev)
     det_s = _cat(det_scores_list, 0, torch.float32, dev)
-    wh = _to_device_async([[m["img_shape"][1], m["img_shape"][0]] for m in img_metas] or [[1, 1]], torch.float32, dev)
+    wh = _lib.small_to_device([[m["img_shape"][1], m["img_shape"][0]] for m in img_metas] or [[1, 1]], torch.float32, dev)
     cost, offs_dev, offs = match_cost_batch(bbox_preds, cls_scores, gt_b, gt_l, counts, wh, assigner._cost_params())
     res = lsap_batch(cost, offs_dev, offs, Q, want_pairs=True, want_assign=False)
     pair_offs = res["pair_offsets"]
@@ -236,16 +227,13 @@ def unsup_gmm_filter(cls_scores, bbox_preds, gt_bboxes_list, gt_labels_list, gt_
     if num_pairs > cap:
         raise ValueError(f"unsup_gmm_filter: {num_pairs} matched pairs exceed this rank's capacity {cap} "
                          f"(num_imgs x max_per_img)")
-    pair_dev = _to_device_async(pair_offs, torch.int32, dev)
-    lib = _lib.lib()
+    pair_dev = _lib.small_to_device(pair_offs, torch.int32, dev)
     seg = torch.empty(cap + 1, dtype=torch.float32, device=dev)
     seg_i = seg.view(torch.int32)
     rows = res["rows"] if res["rows"].numel() else None
     cols = res["cols"]
-    with torch.cuda.device(dev):
-        rc = lib.semidetr_gmm_match_costs_f32(_lib.current_stream_ptr(), _p(cost), _p(offs_dev), _p(pair_dev), _p(rows),
-                                              _p(cols if num_pairs else None), B, Q, num_pairs, cap, _p(seg), _p(seg_i[cap:]))
-    _lib.check(rc, "semidetr_gmm_match_costs_f32")
+    _lib.call("semidetr_gmm_match_costs_f32", dev, cost, offs_dev, pair_dev, rows, cols if num_pairs else None, B, Q,
+              num_pairs, cap, seg, seg_i[cap:])
     gathered = gather_segments(seg, group)
     W = gathered.shape[0]
     thr, det = _fit(gathered, cap + 1, segment_counts(gathered), cap + 1, W, cap, 0, 1e-5, 1e-3, 100, True)
@@ -257,12 +245,8 @@ def unsup_gmm_filter(cls_scores, bbox_preds, gt_bboxes_list, gt_labels_list, gt_
             torch.empty((B * slot, 4), dtype=torch.float32, device=dev),
             torch.empty(B * slot, dtype=torch.int64, device=dev), torch.empty(B * slot, dtype=torch.float32, device=dev))
     out_counts = torch.empty(2 * B, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.semidetr_gmm_double_filter_f32(
-            _lib.current_stream_ptr(), _p(seg), _p(pair_dev), _p(cols if num_pairs else None), _p(thr), _p(gt_b), _p(gt_l),
-            _p(gt_s), _p(det_b), _p(det_l), _p(det_s), _p(offs_dev), B, max(counts) if counts else 0, ctypes.c_float(base_thr),
-            slot, *[_p(t) for t in outs], _p(out_counts))
-    _lib.check(rc, "semidetr_gmm_double_filter_f32")
+    _lib.call("semidetr_gmm_double_filter_f32", dev, seg, pair_dev, cols if num_pairs else None, thr, gt_b, gt_l, gt_s, det_b,
+              det_l, det_s, offs_dev, B, max(counts) if counts else 0, base_thr, slot, *outs, out_counts)
     words = torch.cat([out_counts, res["status"], det["info"]])
     pending = PendingGmmFilter(outs, thr, seg, cols, pair_offs, slot, [t.dtype for t in gt_labels_list], words)
     return pending.result() if wait else pending

@@ -6,16 +6,10 @@ The reference evaluates ~10 elementwise torch kernels forward and as many backwa
 loss sum and its gradient come out of one streaming pass.  ``forward_logits`` additionally folds the
 ``cls_scores.sigmoid()`` of the call site (dino_detr_ssod_head.py:693-694) into the same pass.
 """
-import ctypes
-
 import torch
 from torch import nn
 
 from . import _lib
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 class _TalLossSum(torch.autograd.Function):
@@ -29,14 +23,11 @@ class _TalLossSum(torch.autograd.Function):
         xin = x.detach().to(torch.float32).contiguous()
         tg = target.detach().to(device=x.device, dtype=torch.int64).contiguous()
         mt = metric.detach().to(device=x.device, dtype=torch.float32).contiguous()
-        lib = _lib.lib()
-        ws = torch.empty(int(lib.semidetr_tal_loss_workspace_bytes()), dtype=torch.uint8, device=x.device)
+        ws = torch.empty(int(_lib.lib().semidetr_tal_loss_workspace_bytes()), dtype=torch.uint8, device=x.device)
         out = torch.empty(1, dtype=torch.float32, device=x.device)
         grad = torch.empty_like(xin) if x.requires_grad else None
-        with torch.cuda.device(x.device):
-            rc = lib.semidetr_tal_loss_f32(_lib.current_stream_ptr(), _p(xin), _p(tg), _p(mt), xin.shape[0], xin.shape[1],
-                                           float(gamma), int(bool(input_is_prob)), _p(ws), _p(out), _p(grad))
-        _lib.check(rc, "semidetr_tal_loss_f32")
+        _lib.call("semidetr_tal_loss_f32", x.device, xin, tg, mt, xin.shape[0], xin.shape[1], float(gamma),
+                  int(bool(input_is_prob)), ws, out, grad)
         ctx.save_for_backward(grad)
         ctx.in_dtype = x.dtype
         return out[0]

@@ -7,7 +7,6 @@ positionally in ``named_parameters()`` order, frozen ones included, buffers unto
 The arithmetic runs in ``csrc/ema.hip`` through ``semidetr_ema_multi_f32``; the device-side pointer table
 is built once and reused while the parameter storages stay where they are.
 """
-import ctypes
 from bisect import bisect_right
 
 import torch
@@ -65,12 +64,8 @@ class _EmaTable:
                 tuple(s.numel() for s, _ in pairs))
 
     def launch(self, momentum):
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().semidetr_ema_multi_f32(
-                _lib.current_stream_ptr(), ctypes.c_void_p(self.tptr.data_ptr()),
-                ctypes.c_void_p(self.sptr.data_ptr()), ctypes.c_void_p(self.numel.data_ptr()),
-                ctypes.c_void_p(self.starts.data_ptr()), self.num_tensors, self.total_blocks, float(momentum))
-        _lib.check(rc, "semidetr_ema_multi_f32")
+        _lib.call("semidetr_ema_multi_f32", self.device, self.tptr, self.sptr, self.numel, self.starts, self.num_tensors,
+                  self.total_blocks, float(momentum))
 
 
 _table_cache = {}
@@ -131,11 +126,7 @@ def ema_update_flat_(teacher_flat, student_flat, momentum):
             and student_flat.dtype == torch.float32 and teacher_flat.is_contiguous()
             and student_flat.is_contiguous() and teacher_flat.numel() == student_flat.numel()):
         raise RuntimeError("ema_update_flat_: need two contiguous fp32 GPU tensors of equal size")
-    with torch.cuda.device(teacher_flat.device):
-        rc = _lib.lib().semidetr_ema_flat_f32(
-            _lib.current_stream_ptr(), ctypes.c_void_p(teacher_flat.data_ptr()),
-            ctypes.c_void_p(student_flat.data_ptr()), ctypes.c_int64(teacher_flat.numel()), float(momentum))
-    _lib.check(rc, "semidetr_ema_flat_f32")
+    _lib.call("semidetr_ema_flat_f32", teacher_flat.device, teacher_flat, student_flat, teacher_flat.numel(), float(momentum))
 
 
 class MeanTeacher(_HookBase):

@@ -10,15 +10,9 @@
 * ``teacher_pseudo_labels`` chains both on the device: one host sync for the whole batch.
 * ``transform_bboxes`` replaces ``Transform2D.transform_bboxes`` (detr_ssod/models/utils/bbox_utils.py:167-192).
 """
-import ctypes
-
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 def filter_pseudo_labels(proposal_box_list, proposal_label_list, return_threshold=False):
@@ -30,25 +24,18 @@ def filter_pseudo_labels(proposal_box_list, proposal_label_list, return_threshol
     dev = proposal_box_list[0].device
     if not dev.type == "cuda":
         raise RuntimeError("filter_pseudo_labels: tensors must live on the GPU (no CPU fallback)")
-    counts = [int(p.size(0)) for p in proposal_box_list]
-    offs = [0]
-    for c in counts:
-        offs.append(offs[-1] + c)
+    offs, offs_dev = _lib.offsets([int(p.size(0)) for p in proposal_box_list], dev)
     total = offs[-1]
     prop = torch.cat([p.reshape(-1, 5) for p in proposal_box_list]).to(torch.float32).contiguous()
     lab = torch.cat([l.reshape(-1) for l in proposal_label_list]).to(torch.int64).contiguous()
-    offs_dev = torch.tensor(offs, dtype=torch.int32, device=dev)
     out_boxes = torch.empty((total, 4), dtype=torch.float32, device=dev)
     out_labels = torch.empty(total, dtype=torch.int64, device=dev)
     out_scores = torch.empty(total, dtype=torch.float32, device=dev)
     out_keep = torch.empty(total, dtype=torch.int32, device=dev)
     out_count = torch.empty(B, dtype=torch.int32, device=dev)
     out_thr = torch.empty(B, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().semidetr_pseudo_label_filter_f32(
-            _lib.current_stream_ptr(), _p(prop), _p(lab), _p(offs_dev), _p(None), B, _p(out_boxes), _p(out_labels),
-            _p(out_scores), _p(out_keep), _p(out_count), _p(out_thr))
-    _lib.check(rc, "semidetr_pseudo_label_filter_f32")
+    _lib.call("semidetr_pseudo_label_filter_f32", dev, prop, lab, offs_dev, None, B, out_boxes, out_labels, out_scores,
+              out_keep, out_count, out_thr)
     kept = out_count.tolist()          # the one host sync: list lengths are data dependent
     det_bboxes = [out_boxes[offs[b]:offs[b] + kept[b]] for b in range(B)]
     det_labels = [out_labels[offs[b]:offs[b] + kept[b]].to(proposal_label_list[b].dtype) for b in range(B)]
@@ -59,13 +46,7 @@ def filter_pseudo_labels(proposal_box_list, proposal_label_list, return_threshol
 
 
 def _img_hw(img_metas, dev):
-    return _lib_small([[float(m["img_shape"][0]), float(m["img_shape"][1])] for m in img_metas], torch.float32, dev)
-
-
-def _lib_small(values, dtype, dev):
-    """Small host list -> device tensor through pinned memory (no stream sync)."""
-    t = torch.tensor(values, dtype=dtype)
-    return t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else t.to(dev)
+    return _lib.small_to_device([[float(m["img_shape"][0]), float(m["img_shape"][1])] for m in img_metas], torch.float32, dev)
 
 
 def _nms_batch(cls_scores, bbox_preds, img_metas, score_thr, iou_threshold, max_per_img):
@@ -80,16 +61,12 @@ def _nms_batch(cls_scores, bbox_preds, img_metas, score_thr, iou_threshold, max_
     logits = cls_scores.detach().to(torch.float32).contiguous()
     boxes = bbox_preds.detach().to(torch.float32).contiguous()
     hw = _img_hw(img_metas, dev)
-    lib = _lib.lib()
-    ws = torch.empty(max(int(lib.semidetr_nms_workspace_bytes(B, Q, C)), 16), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(_lib.lib().semidetr_nms_workspace_bytes(B, Q, C)), 16), dtype=torch.uint8, device=dev)
     dets = torch.empty((B, max_per_img, 5), dtype=torch.float32, device=dev)
     labels = torch.empty((B, max_per_img), dtype=torch.int64, device=dev)
     count = torch.empty(B, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.semidetr_pseudo_nms_f32(_lib.current_stream_ptr(), _p(logits), _p(boxes), _p(hw), B, Q, C,
-                                         float(score_thr), float(iou_threshold), int(max_per_img), _p(ws),
-                                         ws.numel(), _p(dets), _p(labels), _p(count))
-    _lib.check(rc, "semidetr_pseudo_nms_f32")
+    _lib.call("semidetr_pseudo_nms_f32", dev, logits, boxes, hw, B, Q, C, float(score_thr), float(iou_threshold),
+              int(max_per_img), ws, ws.numel(), dets, labels, count)
     return dets, labels, count
 
 
@@ -137,17 +114,14 @@ def teacher_pseudo_labels(cls_scores, bbox_preds, img_metas, score_thr=0.01, iou
     ``wait=False`` a ``PendingPseudoLabels`` whose ``result()`` gives the same lists later (one event wait)."""
     dets, labels, count = _nms_batch(cls_scores, bbox_preds, img_metas, score_thr, iou_threshold, max_per_img)
     B, dev = dets.shape[0], dets.device
-    offs = _lib_small([b * max_per_img for b in range(B + 1)], torch.int32, dev)
+    offs = _lib.small_to_device([b * max_per_img for b in range(B + 1)], torch.int32, dev)
     out_boxes = torch.empty((B * max_per_img, 4), dtype=torch.float32, device=dev)
     out_labels = torch.empty(B * max_per_img, dtype=torch.int64, device=dev)
     out_scores = torch.empty(B * max_per_img, dtype=torch.float32, device=dev)
     out_count = torch.empty(B, dtype=torch.int32, device=dev)
     out_thr = torch.empty(B, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().semidetr_pseudo_label_filter_f32(
-            _lib.current_stream_ptr(), _p(dets), _p(labels), _p(offs), _p(count), B, _p(out_boxes), _p(out_labels),
-            _p(out_scores), _p(None), _p(out_count), _p(out_thr))
-    _lib.check(rc, "semidetr_pseudo_label_filter_f32")
+    _lib.call("semidetr_pseudo_label_filter_f32", dev, dets, labels, offs, count, B, out_boxes, out_labels, out_scores,
+              None, out_count, out_thr)
     pending = PendingPseudoLabels(dets, labels, out_boxes, out_labels, out_scores, torch.stack([count, out_count]),
                                   max_per_img)
     return pending.result(return_proposals) if wait else pending
@@ -168,21 +142,14 @@ def transform_bboxes(bbox, M, out_shape):
     if dev.type != "cuda":
         raise RuntimeError("transform_bboxes: tensors must live on the GPU (no CPU fallback)")
     counts = [int(b.shape[0]) for b in boxes]
-    offs = [0]
-    for c in counts:
-        offs.append(offs[-1] + c)
-    total = offs[-1]
     out_list = [b for b in boxes]
-    if total:
+    if sum(counts):
+        offs, offs_dev = _lib.offsets(counts, dev)
         cat = torch.cat([b[:, :4].to(torch.float32) for b in boxes]).contiguous()
         mt = torch.stack([m.to(device=dev, dtype=torch.float32).reshape(3, 3) for m in mats]).contiguous()
-        hw = _lib_small([[float(s[0]), float(s[1])] for s in shapes], torch.float32, dev)
-        offs_dev = _lib_small(offs, torch.int32, dev)
-        out = torch.empty((total, 4), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().semidetr_transform_bboxes_f32(_lib.current_stream_ptr(), _p(cat), 4, _p(offs_dev), _p(None),
-                                                          B, max(counts), _p(mt), _p(hw), _p(out))
-        _lib.check(rc, "semidetr_transform_bboxes_f32")
+        hw = _lib.small_to_device([[float(s[0]), float(s[1])] for s in shapes], torch.float32, dev)
+        out = torch.empty((offs[-1], 4), dtype=torch.float32, device=dev)
+        _lib.call("semidetr_transform_bboxes_f32", dev, cat, 4, offs_dev, None, B, max(counts), mt, hw, out)
         out_list = []
         for b in range(B):
             o = out[offs[b]:offs[b + 1]].to(boxes[b].dtype)

@@ -15,7 +15,6 @@ ascending): a total order, so the choice among tied tokens is the lowest indices
 ``forward_with_query`` (transformer.py:1409-1481) has no two-stage block -- it takes its queries from the caller -- so only
 ``forward`` has a use for ``two_stage_queries``.
 """
-import contextlib
 import ctypes
 
 import torch
@@ -23,19 +22,6 @@ import torch
 from . import _lib
 
 MAX_LEVELS, MAX_K = 8, 4096                # SEMIDETR_QSEL_MAX_LEVELS, SEMIDETR_QSEL_MAX_K
-_P = ctypes.c_void_p
-
-
-_NO_GUARD = contextlib.nullcontext()
-
-
-def _guard(dev):
-    """Device guard only where the tensors' device is not the current one (the guard costs more than a launch)."""
-    return _NO_GUARD if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
-
-
-def _stream(dev):
-    return _P(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _require(t, what):
@@ -84,11 +70,7 @@ class _ProposalsFn(torch.autograd.Function):
         out = torch.empty_like(mem)
         prop = torch.empty((N, S, 4), dtype=torch.float32, device=dev)
         valid = torch.empty((N, S), dtype=torch.uint8, device=dev)
-        with _guard(dev):
-            _lib.check(_lib.lib().semidetr_qsel_proposals_f32(
-                _stream(dev), _P(mem.data_ptr()), _P(m.data_ptr()),
-                ctypes.cast(host, _P) if host is not None else None, _P(table.data_ptr()) if table is not None else None,
-                L, N, S, D, _P(out.data_ptr()), _P(prop.data_ptr()), _P(valid.data_ptr())), "semidetr_qsel_proposals_f32")
+        _lib.call("semidetr_qsel_proposals_f32", dev, mem, m, host, table, L, N, S, D, out, prop, valid)
         ctx.save_for_backward(valid)
         ctx.mark_non_differentiable(prop)
         ctx.set_materialize_grads(False)
@@ -102,10 +84,7 @@ class _ProposalsFn(torch.autograd.Function):
         g = _f32(g_out, "grad of output_memory")
         N, S, D = g.shape
         gm = torch.empty_like(g)
-        with _guard(g.device):
-            _lib.check(_lib.lib().semidetr_qsel_proposals_backward_f32(
-                _stream(g.device), _P(g.data_ptr()), _P(valid.data_ptr()), N, S, D, _P(gm.data_ptr())),
-                "semidetr_qsel_proposals_backward_f32")
+        _lib.call("semidetr_qsel_proposals_backward_f32", g.device, g, valid, N, S, D, gm)
         return gm, None, None
 
 
@@ -129,21 +108,15 @@ class _SelectFn(torch.autograd.Function):
         N, S, C = lg.shape
         D = mem.shape[2]
         dev = lg.device
-        lib = _lib.lib()
-        ws_bytes = lib.semidetr_qsel_topk_workspace_bytes(N, S)
+        ws_bytes = _lib.lib().semidetr_qsel_topk_workspace_bytes(N, S)
         ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
         idx = torch.empty((N, k), dtype=torch.int64, device=dev)
         inv = torch.empty((N, S), dtype=torch.int32, device=dev)
         ref = torch.empty((N, k, 4), dtype=torch.float32, device=dev)
         init_box, ref_enc = torch.empty_like(ref), torch.empty_like(ref)
         tgt = torch.empty((N, k, D), dtype=torch.float32, device=dev)
-        with _guard(dev):
-            st = _stream(dev)
-            _lib.check(lib.semidetr_qsel_topk_f32(st, _P(lg.data_ptr()), N, S, C, k, _P(ws.data_ptr()), ws_bytes,
-                                                  _P(idx.data_ptr()), _P(inv.data_ptr())), "semidetr_qsel_topk_f32")
-            _lib.check(lib.semidetr_qsel_gather_f32(st, _P(idx.data_ptr()), _P(cd.data_ptr()), _P(pr.data_ptr()),
-                                                    _P(mem.data_ptr()), N, S, k, D, _P(ref.data_ptr()), _P(init_box.data_ptr()),
-                                                    _P(tgt.data_ptr()), _P(ref_enc.data_ptr())), "semidetr_qsel_gather_f32")
+        _lib.calls(dev, ("semidetr_qsel_topk_f32", lg, N, S, C, k, ws, ws_bytes, idx, inv),
+                   ("semidetr_qsel_gather_f32", idx, cd, pr, mem, N, S, k, D, ref, init_box, tgt, ref_enc))
         ctx.sizes = (N, S, k, D)
         ctx.save_for_backward(inv, ref_enc)
         ctx.mark_non_differentiable(idx, init_box)
@@ -162,11 +135,7 @@ class _SelectFn(torch.autograd.Function):
         g_ref, g_tgt, g_enc = [None if g is None else _f32(g, "gradient") for g in (g_ref, g_tgt, g_enc)]
         gc = torch.empty((N, S, 4), dtype=torch.float32, device=dev) if want_c else None
         gm = torch.empty((N, S, D), dtype=torch.float32, device=dev) if want_m else None
-        ptr = lambda t: None if t is None else _P(t.data_ptr())      # noqa: E731
-        with _guard(dev):
-            _lib.check(_lib.lib().semidetr_qsel_gather_backward_f32(
-                _stream(dev), _P(inv.data_ptr()), ptr(g_ref), ptr(g_tgt), ptr(g_enc), _P(ref_enc.data_ptr()), N, S,
-                k, D, ptr(gc), ptr(gm)), "semidetr_qsel_gather_backward_f32")
+        _lib.call("semidetr_qsel_gather_backward_f32", dev, inv, g_ref, g_tgt, g_enc, ref_enc, N, S, k, D, gc, gm)
         return None, gc, None, gm, None
 
 

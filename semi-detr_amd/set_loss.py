@@ -19,7 +19,6 @@ import torch.distributed as dist
 from torch import nn
 
 from . import _lib
-from .matcher import _offsets, _to_device_async
 from .targets import _targets_stacked
 
 MATCHED, DN, WARMUP = 0, 1, 2             # SEMIDETR_SET_LOSS_*
@@ -90,7 +89,7 @@ class SetLossSegment:
             if len(counts) != self.B or any(n > self.single_pad for n in counts):
                 raise ValueError(f"set_loss: dn needs one gt list per image and G_b <= single_pad ({counts}, "
                                  f"single_pad {self.single_pad})")
-            _, self.gt_offsets = _offsets(counts, dev)
+            _, self.gt_offsets = _lib.offsets(counts, dev)
             if sum(counts):
                 self.gt_boxes = torch.cat([g.reshape(-1, 4) for g in gt_bboxes]).to(dev, torch.float32).contiguous()
                 self.gt_labels = torch.cat([g.reshape(-1) for g in gt_labels]).to(dev, torch.int64).contiguous()
@@ -136,8 +135,7 @@ def _forward(segs, flat, group, finalize=True):
     ``finalize=False``: the raw stats and normaliser inputs only -- no normalisers, so no collective either (losses and
     scales are then left unset)."""
     tab = _table(segs, flat)
-    lib = _lib.lib()
-    nbytes = int(lib.semidetr_set_loss_workspace_bytes(tab, len(segs)))
+    nbytes = int(_lib.lib().semidetr_set_loss_workspace_bytes(tab, len(segs)))
     if nbytes < 0:
         _lib.check(nbytes, "semidetr_set_loss_workspace_bytes")
     T = sum(sg.nl for sg in segs)
@@ -148,21 +146,15 @@ def _forward(segs, flat, group, finalize=True):
     losses = torch.empty((T, NUM_TERMS), dtype=torch.float32, device=dev)
     scales = torch.empty((T, NUM_TERMS), dtype=torch.float32, device=dev)
     world = _world(group) if finalize else 1
-    P = ctypes.c_void_p
     reduced = None
-    with torch.cuda.device(dev):
-        fin = finalize and world == 1
-        _lib.check(lib.semidetr_set_loss_forward_f32(_lib.current_stream_ptr(), tab, len(segs), P(ws.data_ptr()), nbytes,
-                                                     P(stats.data_ptr()), P(norms.data_ptr()),
-                                                     P(losses.data_ptr() if fin else None),
-                                                     P(scales.data_ptr() if fin else None)), "semidetr_set_loss_forward_f32")
-        if finalize and not fin:
+    fin = finalize and world == 1
+    _lib.call("semidetr_set_loss_forward_f32", dev, tab, len(segs), ws, nbytes, stats, norms, losses if fin else None,
+              scales if fin else None)
+    if finalize and not fin:
+        with _lib.device_guard(dev):                         # the collective runs with the tensors' device current
             reduced = norms / world                          # mmdet reduce_mean: divide, then all-reduce SUM
             dist.all_reduce(reduced, op=dist.ReduceOp.SUM, group=group)
-            _lib.check(lib.semidetr_set_loss_finalize_f32(_lib.current_stream_ptr(), tab, len(segs), P(stats.data_ptr()),
-                                                          P(norms.data_ptr()), P(reduced.data_ptr()),
-                                                          P(losses.data_ptr()), P(scales.data_ptr())),
-                       "semidetr_set_loss_finalize_f32")
+        _lib.call("semidetr_set_loss_finalize_f32", dev, tab, len(segs), stats, norms, reduced, losses, scales)
     return dict(stats=stats, norms=norms, norms_reduced=reduced, losses=losses, scales=scales)
 
 
@@ -192,11 +184,7 @@ class _SetLossFn(torch.autograd.Function):
         out = [torch.empty(m[0], dtype=torch.float32, device=scales.device) if (w and m is not None) else None
                for w, m in zip(want, ctx.in_meta)]
         tab = _table(ctx.segs, flat, out)
-        with torch.cuda.device(scales.device):
-            _lib.check(_lib.lib().semidetr_set_loss_backward_f32(_lib.current_stream_ptr(), tab, len(ctx.segs),
-                                                                 ctypes.c_void_p(scales.data_ptr()),
-                                                                 ctypes.c_void_p(gout.data_ptr())),
-                       "semidetr_set_loss_backward_f32")
+        _lib.call("semidetr_set_loss_backward_f32", scales.device, tab, len(ctx.segs), scales, gout)
         out = [o.to(m[1]) if o is not None and o.dtype != m[1] else o for o, m in zip(out, ctx.in_meta)]
         return (None, None, None) + tuple(out)
 
@@ -249,7 +237,7 @@ def loss_set(self, all_cls_scores, all_bbox_preds, enc_cls_scores, enc_bbox_pred
         box_t = torch.cat([box_t, enc_bbox_preds.detach().reshape(B, Q, 4)])
         gts, labs, metas = gts + gt_bboxes_list, labs + [torch.zeros_like(g) for g in gt_labels_list], metas + img_metas
     t = _targets_stacked(self, cls_t.float(), box_t.float(), gts, labs, metas, check=False)
-    img_wh = _to_device_async([[float(m["img_shape"][1]), float(m["img_shape"][0])] for m in img_metas], torch.float32, dev)
+    img_wh = _lib.small_to_device([[float(m["img_shape"][1]), float(m["img_shape"][0])] for m in img_metas], torch.float32, dev)
 
     iou = self.loss_iou
     common = dict(img_wh=img_wh, l1_weight=_weight(self.loss_bbox, "loss_weight", 1.0),
@@ -327,10 +315,7 @@ class _FocalSum(torch.autograd.Function):
         gout = torch.nn.functional.pad(g.reshape(1).float(), (0, NUM_TERMS - 1))
         grad = torch.empty_like(ctx.x, memory_format=torch.contiguous_format)
         tab = _table([ctx.seg], [ctx.x, None], [grad, None])
-        with torch.cuda.device(grad.device):
-            _lib.check(_lib.lib().semidetr_set_loss_backward_f32(_lib.current_stream_ptr(), tab, 1, None,
-                                                                 ctypes.c_void_p(gout.data_ptr())),
-                       "semidetr_set_loss_backward_f32")
+        _lib.call("semidetr_set_loss_backward_f32", grad.device, tab, 1, None, gout)
         return grad[0, 0].to(ctx.in_dtype), None, None, None, None
 
 
