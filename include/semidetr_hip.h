@@ -619,6 +619,41 @@ int semidetr_qsel_gather_backward_f32(void *stream, const int32_t *inverse, cons
                                       const float *grad_ref_enc, const float *ref_enc, int N, int S, int k, int D,
                                       float *grad_coord, float *grad_memory);
 
+/* ---------------------------------------------------------------------------------------------
+ * Detection decode (ABI 7, additive): what evaluation and inference run on every image after the head.
+ *
+ * Replaces  get_bboxes (for_pseudo_label=False)       detr_od/models/dense_heads/dino_detr_ssod_head.py:1316-1330
+ *           _get_bboxes_single, sigmoid + flat topk   dino_detr_ssod_head.py:1366-1369, 1396-1400; dino_detr_head.py:1129-1137
+ *           box decode, clamp, rescale, cat           dino_detr_ssod_head.py:1404-1413; dino_detr_head.py:1143-1152
+ *           bbox2result                               thirdparty/mmdetection/mmdet/core/bbox/transforms.py:100-117
+ *           (the NMS branch of the same function is semidetr_pseudo_nms_f32; the softmax branch, dino_detr_head.py:1138-1141,
+ *           is not built)
+ *
+ * fp32, on `stream`, two launches for the whole batch, no host synchronisation, nothing read back, no memset, no float
+ * atomics; bitwise reproducible.
+ *
+ * semidetr_det_decode_f32 -- cls_logits (B, Q, C) raw logits, bbox_pred (B, Q, 4) normalised cxcywh, img_hw (B, 2) = (height,
+ *   width) of img_shape, scale_factor (B, 4) on the device or NULL (rescale=False).  Per image the k largest of the Q * C
+ *   LOGITS, sorted by (logit descending, flat index q * C + c ascending): a total order (NaN above +inf, -0 == +0) and one valid
+ *   resolution of every tie torch.topk over the sigmoids leaves open.  For rank r with flat index i:
+ *     out_labels (B, k) int64 = i % C;  q = i / C;  score = 1 / (1 + exp(-logit))
+ *     (x1, y1, x2, y2) = (cx - .5 w, cy - .5 h, cx + .5 w, cy + .5 h) * (W, H, W, H), clamped to [0, W] / [0, H], then, with a
+ *     scale_factor, divided by it element-wise (IEEE correctly rounded);  out_dets (B, k, 5) = (x1, y1, x2, y2, score).
+ *   With out_dets_by_class (B, k, 5) and out_class_offsets (B, C + 1) int32 (both or neither): the same rows stably partitioned
+ *   by label (score order kept inside a class); class c of image b is rows [offsets[b][c], offsets[b][c + 1]).
+ *   workspace: semidetr_det_workspace_bytes(batch, num_query, num_classes, k) bytes, 8-byte aligned (0 for sizes outside the
+ *   limits); its contents need no initialisation.
+ * Limits: 1 <= k <= min(Q * C, SEMIDETR_DET_MAX_K) (SEMIDETR_E_BADARG for k outside [1, Q * C], SEMIDETR_E_TOOLARGE above
+ *   SEMIDETR_DET_MAX_K), Q * C < 2^31, batch <= 65535.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_DET_MAX_K 2048
+size_t semidetr_det_workspace_bytes(int batch, int num_query, int num_classes, int k);
+int semidetr_det_decode_f32(void *stream, const float *cls_logits, const float *bbox_pred, const float *img_hw,
+                            const float *scale_factor /* (B, 4) device, NULL = no rescale */, int batch, int num_query,
+                            int num_classes, int k, void *workspace, size_t workspace_bytes, float *out_dets /* (B, k, 5) */,
+                            int64_t *out_labels /* (B, k) */, float *out_dets_by_class /* (B, k, 5), nullable */,
+                            int32_t *out_class_offsets /* (B, C + 1), nullable together */);
+
 #ifdef __cplusplus
 }
 #endif

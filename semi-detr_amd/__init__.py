@@ -27,6 +27,7 @@ from .gmm_filter import (GmmFilterResult, PendingGmmFilter, fit_gmm, fit_gmm_thr
 from .set_loss import FocalLoss, SetLossSegment, loss_set, set_losses  # noqa: E402,F401
 from .dn_query import consistency_queries, prepare_for_cdn, prepare_for_cdn_plus, prepare_unsup_cdn  # noqa: E402,F401
 from .query_select import gen_encoder_output_proposals, select_queries, two_stage_queries  # noqa: E402,F401
+from .detect import PendingDetections, detection_results, get_bboxes  # noqa: E402,F401
 from .pseudo_label import (filter_pseudo_labels, get_bboxes_for_pseudo_label, teacher_pseudo_labels,  # noqa: E402,F401
                            transform_bboxes)
 
@@ -36,4 +37,5 @@ __all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttn", 
            "transform_bboxes", "TargetAssigner", "get_targets", "get_targets_layers", "fit_gmm", "fit_gmm_threshold",
            "fit_gmm_threshold_segments", "unsup_gmm_filter", "GmmFilterResult", "PendingGmmFilter",
            "FocalLoss", "SetLossSegment", "loss_set", "set_losses", "prepare_for_cdn", "prepare_for_cdn_plus",
-           "prepare_unsup_cdn", "consistency_queries", "gen_encoder_output_proposals", "select_queries", "two_stage_queries"]
+           "prepare_unsup_cdn", "consistency_queries", "gen_encoder_output_proposals", "select_queries", "two_stage_queries",
+           "get_bboxes", "detection_results", "PendingDetections"]

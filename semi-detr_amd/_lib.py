@@ -82,6 +82,9 @@ SIGNATURES = {
     "semidetr_qsel_topk_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
     "semidetr_qsel_gather_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 4),
     "semidetr_qsel_gather_backward_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 2),
+    # detection decode at evaluation / inference time (detect.py)
+    "semidetr_det_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
+    "semidetr_det_decode_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p, ctypes.c_size_t] + [c_void_p] * 4),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so
