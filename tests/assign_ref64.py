@@ -141,6 +141,12 @@ def log_(a):
     return _r(np.log(a[0]), np.where(r < 1, -np.log1p(-np.minimum(r, 0.5 + 0.5 * r)), np.inf))
 
 
+def log1p_(a):
+    """log1pf: log_ of 1 + t without the rounding of the sum (the loss kernels' softplus; tests/loss_ref64.py)."""
+    r = a[1] / np.abs(1.0 + a[0])
+    return _r(np.log1p(a[0]), np.where(r < 1, -np.log1p(-np.minimum(r, 0.5 + 0.5 * r)), np.inf))
+
+
 def pow_(a, g):
     g = float(g)
     v = np.power(a[0], g)
