@@ -16,58 +16,20 @@
 // logits whose fp32 sigmoids coincide).  Order: logit descending, flat index q * C + c ascending; NaN above +inf; -0 == +0.
 // Integer LDS atomics only; no float atomics, no scratch.
 #include "common.h"
+#include "select.h"
 
 namespace {
 
+using semidetr::kHistStride;
+using semidetr::order_key;
+using semidetr::sigmoidf_;
+
 constexpr int kThreads = 1024;
 constexpr int kChunk = 8192;                          // logits per workgroup of the first stage: 32 KB of keys
-constexpr int kHistCopies = 16, kHistStride = 257;
+constexpr int kHistCopies = 16;
 constexpr size_t kLdsBudget = 160 * 1024 - 2048;      // dynamic LDS of the merge kernel; the rest is its static part
 
 typedef unsigned long long u64;
-
-__device__ inline float sigmoidf_(float x) { return __fdiv_rn(1.f, 1.f + expf(-x)); }
-
-// the integer that orders like the float: NaN (any sign) above +inf, -0 == +0 (as in query_select.hip)
-__device__ inline unsigned order_key(float v)
-{
-    if (v != v) return 0xFFFFFFFFu;
-    if (v == 0.f) v = 0.f;
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ inline void clear_hist(int *hist, int tid)
-{
-    for (int i = tid; i < kHistCopies * kHistStride; i += kThreads) hist[i] = 0;
-}
-
-// hist -> the digit that holds the s_remaining-th largest element; s_remaining becomes its rank inside that digit.  Thread d sums
-// the bins above d (256 broadcast reads at a fixed trip count, so they pipeline; one thread walking down the bins with an early
-// exit pays an LDS round trip per bin, ~10 us per pass), and the one thread whose bin the rank falls into publishes.
-__device__ inline void pick_digit(const int *hist, int *bins, int *s_digit, int *s_remaining, int tid)
-{
-    if (tid < 256) {
-        int v = 0;
-        for (int cp = 0; cp < kHistCopies; ++cp) v += hist[cp * kHistStride + tid];
-        bins[tid] = v;
-    }
-    __syncthreads();
-    const int rem = *s_remaining;
-    int above = 0;
-    bool mine = false;
-    if (tid < 256) {
-#pragma unroll 16
-        for (int j = 0; j < 256; ++j) above += j > tid ? bins[j] : 0;
-        mine = above < rem && rem <= above + bins[tid];
-    }
-    __syncthreads();                                                   // every thread has read s_remaining
-    if (mine) {
-        *s_digit = tid;
-        *s_remaining = rem - above;
-    }
-    __syncthreads();
-}
 
 // ---- stage 1: the min(k, chunk) largest keys of one chunk.  grid (chunks, B)
 __global__ __launch_bounds__(kThreads) void det_chunk_select_kernel(const float *__restrict__ logits, int QC, int k, int kk,
@@ -78,7 +40,7 @@ __global__ __launch_bounds__(kThreads) void det_chunk_select_kernel(const float 
     __shared__ int bins[256];
     __shared__ int s_wave[kThreads / 64];
     __shared__ int s_digit, s_remaining, s_fill, s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int chunk = blockIdx.x, b = blockIdx.y;
     const int first = chunk * kChunk;                                  // < QC: the grid has ceil(QC / kChunk) chunks
     const int len = QC - first < kChunk ? QC - first : kChunk;
@@ -90,58 +52,20 @@ __global__ __launch_bounds__(kThreads) void det_chunk_select_kernel(const float 
     __syncthreads();
     unsigned prefix = 0, pmask = 0;
     for (int pass = 3; pass >= 0; --pass) {
-        clear_hist(hist, tid);
-        __syncthreads();
-        for (int i = tid; i < len; i += kThreads) {
-            const unsigned u = keys[i];
-            if ((u & pmask) == prefix) atomicAdd(&hist[(lane & (kHistCopies - 1)) * kHistStride + (int)((u >> (8 * pass)) & 255)], 1);
-        }
-        __syncthreads();
-        pick_digit(hist, bins, &s_digit, &s_remaining, tid);
+        semidetr::histogram_pass<kThreads, kHistCopies>(hist, keys, len, prefix, pmask, pass);
+        // 1 <= s_remaining <= words counted: it starts as want = min(k, len) with k >= 1 (launcher) and len >= 1 (grid), against
+        // all len keys, and every pass leaves the rank inside the chosen digit, whose keys are the next pass's
+        semidetr::pick_digit<kThreads, kHistCopies>(hist, bins, &s_digit, &s_remaining);
         prefix |= (unsigned)s_digit << (8 * pass);
         pmask |= 0xFFu << (8 * pass);
     }
     const int ties = s_remaining;
     // every key above the want-th, and the first `ties` positions, in index order, that equal it
-    for (int i0 = 0; i0 < len; i0 += kThreads) {
-        const int i = i0 + tid;
-        const unsigned u = i < len ? keys[i] : 0u;
-        const bool above = i < len && u > prefix, tie = i < len && u == prefix;
-        const u64 ballot = __ballot(tie);
-        if (lane == 0) s_wave[wave] = __popcll(ballot);
-        __syncthreads();
-        int before = s_base;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        const int rank = before + __popcll(ballot & ((1ull << lane) - 1ull));
-        if (above || (tie && rank < ties)) {
-            const int slot = atomicAdd(&s_fill, 1);
-            if (slot < kk) dst[slot] = ((u64)u << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)(first + i));
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int t = 0;
-            for (int w = 0; w < kThreads / 64; ++w) t += s_wave[w];
-            s_base += t;
-        }
-        __syncthreads();
-    }
+    semidetr::collect_with_ties<kThreads>(keys, len, prefix, ties, s_wave, &s_base, [&](int i, unsigned u) {
+        const int slot = atomicAdd(&s_fill, 1);
+        if (slot < kk) dst[slot] = ((u64)u << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)(first + i));
+    });
     for (int i = want + tid; i < kk; i += kThreads) dst[i] = 0;         // below every real word: the smallest key is ~(-inf) > 0
-}
-
-// bitonic sort, descending, of the n (a power of two) words of v
-__device__ inline void sort_desc(u64 *v, int n, int tid)
-{
-    for (int size = 2; size <= n; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (n >> 1); t += kThreads) {
-                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                const bool desc = (lo & size) == 0;
-                const u64 a = v[lo], c = v[hi];
-                if ((a < c) == desc) { v[lo] = c; v[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
 }
 
 struct Row { float x1, y1, x2, y2, score; };
@@ -189,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void det_merge_decode_kernel(const u64 *_
     int *hist = reinterpret_cast<int *>(sel + kcap);                                      // 16 448 bytes: keeps 8-byte alignment
     unsigned *flat = reinterpret_cast<unsigned *>(hist + kHistCopies * kHistStride);       // flat index of every rank
     u64 *cand_l = reinterpret_cast<u64 *>(flat + kcap);
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int QC = Q * C;
     const u64 *cg = survivors + (int64_t)b * M;
     if (in_lds)
@@ -202,14 +126,11 @@ __global__ __launch_bounds__(kThreads) void det_merge_decode_kernel(const u64 *_
     // part of them) and there are at least k of them, so after eight passes `prefix` IS the k-th largest word.
     u64 prefix = 0, pmask = 0;
     for (int pass = 7; pass >= 0; --pass) {
-        clear_hist(hist, tid);
-        __syncthreads();
-        for (int i = tid; i < M; i += kThreads) {
-            const u64 u = cand[i];
-            if ((u & pmask) == prefix) atomicAdd(&hist[(lane & (kHistCopies - 1)) * kHistStride + (int)((u >> (8 * pass)) & 255)], 1);
-        }
-        __syncthreads();
-        pick_digit(hist, bins, &s_digit, &s_remaining, tid);
+        semidetr::histogram_pass<kThreads, kHistCopies>(hist, cand, M, prefix, pmask, pass);
+        // 1 <= s_remaining <= words counted: it starts as k >= 1 against all M = chunks * kk words (zero tails included), and
+        // k <= M because kk = k, or kk = kChunk and chunks * kChunk >= Q * C >= k (launcher); every pass leaves the rank inside
+        // the chosen digit, whose words are the next pass's
+        semidetr::pick_digit<kThreads, kHistCopies>(hist, bins, &s_digit, &s_remaining);
         prefix |= (u64)s_digit << (8 * pass);
         pmask |= (u64)0xFF << (8 * pass);
     }
@@ -220,8 +141,7 @@ __global__ __launch_bounds__(kThreads) void det_merge_decode_kernel(const u64 *_
             if (slot < kcap) sel[slot] = u;
         }
     }
-    __syncthreads();
-    sort_desc(sel, kcap, tid);
+    semidetr::bitonic_desc<kThreads>(sel, kcap);
     const float H = img_hw[2 * b], W = img_hw[2 * b + 1];
     const float *sf = scale_factor ? scale_factor + 4 * b : nullptr;
     const float *lg = logits + (int64_t)b * QC, *bx = bbox_pred + (int64_t)b * Q * 4;
@@ -239,8 +159,7 @@ __global__ __launch_bounds__(kThreads) void det_merge_decode_kernel(const u64 *_
     // bbox2result: the same rows ordered by (label ascending, rank ascending) -- stable because the rank is part of the word.
     // The sort is descending, so the words are complemented; the unused slots are 0 and sink to the end.
     for (int r = tid; r < kcap; r += kThreads) sel[r] = r < k ? ~(((u64)(flat[r] % (unsigned)C) << 32) | (unsigned)r) : 0;
-    __syncthreads();
-    sort_desc(sel, kcap, tid);
+    semidetr::bitonic_desc<kThreads>(sel, kcap);
     for (int j = tid; j < k; j += kThreads) {
         const int r = (int)((~sel[j]) & 0xFFFFFFFFull);
         store_row(out_by_class + ((int64_t)b * k + j) * 5, decode_row(lg, bx, flat[r < k ? r : 0], C, H, W, sf));
@@ -256,39 +175,11 @@ __global__ __launch_bounds__(kThreads) void det_merge_decode_kernel(const u64 *_
     }
 }
 
-}  // namespace
-
-namespace {
-
-int next_pow2(int v)
-{
-    int p = 2;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 inline int num_chunks(int64_t QC) { return (int)((QC + kChunk - 1) / kChunk); }
 
 size_t merge_lds_bytes(int M, int kcap, bool in_lds)
 {
     return (size_t)kcap * 12 + (size_t)kHistCopies * kHistStride * 4 + (in_lds ? (size_t)M * 8 : 0);
-}
-
-// dynamic LDS above 64 KB has to be allowed per kernel and per device
-int allow_merge_lds(size_t bytes)
-{
-    if (bytes <= 64 * 1024) return SEMIDETR_OK;
-    static thread_local bool granted[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return semidetr::fail((int)e, "det_decode: hipGetDevice: %s", hipGetErrorString(e));
-    if (dev >= 0 && dev < 64 && granted[dev]) return SEMIDETR_OK;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&det_merge_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kLdsBudget);
-    if (e != hipSuccess)
-        return semidetr::fail((int)e, "det_decode: hipFuncSetAttribute(%zu bytes of LDS): %s", kLdsBudget, hipGetErrorString(e));
-    if (dev >= 0 && dev < 64) granted[dev] = true;
-    return SEMIDETR_OK;
 }
 
 // the checks both entry points share; 0 when (batch, num_query, num_classes, k) is a problem the kernels take
@@ -328,11 +219,12 @@ extern "C" int semidetr_det_decode_f32(void *stream, const float *cls_logits, co
     SEMIDETR_REQUIRE(workspace_bytes >= need && ((uintptr_t)workspace & 7) == 0, SEMIDETR_E_BADARG,
                      "det_decode: workspace of %zu bytes (need %zu, 8-byte aligned)", workspace_bytes, need);
     const int QC = num_query * num_classes;
-    const int chunks = num_chunks(QC), kk = k < kChunk ? k : kChunk, kcap = next_pow2(k);
+    const int chunks = num_chunks(QC), kk = k < kChunk ? k : kChunk, kcap = semidetr::next_pow2(k);
     const int M = chunks * kk;
     const bool in_lds = merge_lds_bytes(M, kcap, true) <= kLdsBudget;
     const size_t lds = merge_lds_bytes(M, kcap, in_lds);
-    if (int rc = allow_merge_lds(lds)) return rc;
+    if (lds > 64 * 1024)       // the fixed budget, not `lds`: one grant per device covers every later shape
+        if (int rc = semidetr::allow_big_lds(&det_merge_decode_kernel, kLdsBudget, "det_decode")) return rc;
     u64 *survivors = static_cast<u64 *>(workspace);
     hipLaunchKernelGGL(det_chunk_select_kernel, dim3(chunks, batch), dim3(kThreads), 0, semidetr::as_stream(stream), cls_logits,
                        QC, k, kk, survivors);

@@ -340,9 +340,7 @@ extern "C" int semidetr_lsap_solve(void *stream, const float *cost, const int32_
     hipStream_t st = semidetr::as_stream(stream);
     const size_t cost_bytes = (size_t)max_gt * (size_t)num_query * sizeof(float);
     if (per <= kLdsLimit && per + cost_bytes <= kLdsBig) {         // solver state AND the cost block in LDS
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lsap_kernel<true, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBig);
-        if (e != hipSuccess) return semidetr::fail((int)e, "lsap: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        if (int rc = semidetr::allow_big_lds(&lsap_kernel<true, true>, kLdsBig, "lsap")) return rc;
         hipLaunchKernelGGL((lsap_kernel<true, true>), dim3(num_problems), dim3(64), per + cost_bytes, st, cost, gt_offsets,
                            gt_labels, num_query, ncmax, nrmax, match_row, match_col, assigned_gt_inds,
                            assigned_labels, status, (char *)nullptr, (size_t)0);

@@ -470,30 +470,7 @@ int pick_split(int forced, int N, int Lq, int M)
 }
 
 
-// dynamic LDS above 64 KB has to be allowed per kernel AND per device (function attributes are per device: ADVICE r02)
-template <typename K>
-int allow_big_lds(K kern, size_t bytes, const char *what)
-{
-    if (bytes <= 64 * 1024) return SEMIDETR_OK;
-    // what was granted, per (kernel, device) of this thread: kernels of one signature share the pointer TYPE, so the
-    // bookkeeping is keyed on the pointer VALUE
-    struct Granted { const void *kern; int dev; size_t bytes; };
-    static thread_local Granted table[32];
-    static thread_local int used = 0;
-    const void *kp = reinterpret_cast<const void *>(kern);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return semidetr::fail((int)e, "%s: hipGetDevice: %s", what, hipGetErrorString(e));
-    Granted *g = nullptr;
-    for (int i = 0; i < used; ++i)
-        if (table[i].kern == kp && table[i].dev == dev) g = &table[i];
-    if (g && g->bytes >= bytes) return SEMIDETR_OK;
-    e = hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return semidetr::fail((int)e, "%s: hipFuncSetAttribute(%zu bytes of LDS): %s", what, bytes, hipGetErrorString(e));
-    if (!g && used < 32) g = &table[used++];
-    if (g) *g = Granted{kp, dev, bytes};           // a full table only costs a repeated hipFuncSetAttribute
-    return SEMIDETR_OK;
-}
+using semidetr::allow_big_lds;      // (kernels of one signature share the pointer TYPE; the grant is keyed on the pointer VALUE)
 
 // ---- which kernel runs the encoder self-attention forward: the patch kernel (msda_fwd_d32<1,4,408>) or the region-window
 //      kernel (msda_rw_d32, LDS windows +- 5 px around a region, five levels +- 4 px).  The second is ~30 % faster while the learned

@@ -12,7 +12,7 @@
 //   Transform2D.transform_bboxes   detr_ssod/models/utils/bbox_utils.py:167-192 (+ bbox2points/points2bbox :18-41)
 //
 // Order: candidates are ranked by LOGIT (any monotonic sigmoid gives the same ranking), equal logits by
-// ascending flat index q * C + c -- a 64-bit key {orderable(logit), ~flat}; all keys are distinct, so the
+// ascending flat index q * C + c -- a 64-bit key {order_key(logit), ~flat}; all keys are distinct, so the
 // result is deterministic although the final list is assembled with atomics.
 //
 // Three launches (after one memset of the per-image scalars):
@@ -27,15 +27,14 @@
 
 #pragma clang fp contract(off)      // every result is one rounded operation, like the reference's separate torch ops
 
+#include "select.h"                 // behind the pragma: it holds for sigmoidf_ as well
+
 namespace {
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ unsigned orderable(float x)      // monotonic float -> unsigned; -0 and +0 compare equal
-{
-    const unsigned u = x == 0.f ? 0u : __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+using semidetr::bitonic_desc;
+using semidetr::kHistStride;
+using semidetr::order_key;
+using semidetr::sigmoidf_;
 
 __device__ __forceinline__ float4 decode_box(const float *bp, float img_h, float img_w)
 {
@@ -118,25 +117,6 @@ __global__ __launch_bounds__(256) void nms_prepare_kernel(const float *__restric
     }
 }
 
-// descending bitonic sort of n2 (power of two) 64-bit keys in LDS by NT threads
-template <int NT>
-__device__ __forceinline__ void bitonic_desc(unsigned long long *keys, int n2)
-{
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int t = threadIdx.x; t < n2 / 2; t += NT) {
-                const int i = 2 * t - (t & (j - 1));          // index with bit j clear
-                const int p = i + j;
-                const unsigned long long a = keys[i], c = keys[p];
-                const bool desc = (i & k) == 0;
-                if (desc ? a < c : a > c) { keys[i] = c; keys[p] = a; }
-            }
-        }
-    }
-    __syncthreads();
-}
-
 // ---- one (class, image): sort the class's candidates, greedy NMS, append the survivors to the image's list.
 // NW wavefronts per problem; the C x B problems spread over the CUs.  The greedy scan runs in chunks of 64 sorted
 // candidates (lane = candidate, every wavefront holds the same chunk): a lane first checks its box against the boxes kept
@@ -169,7 +149,7 @@ __global__ __launch_bounds__(64 * NW) void nms_class_kernel(const float *__restr
         if (q < Q) {
             const float x = logits[((size_t)b * Q + q) * C + c];
             if (sigmoidf_(x) > score_thr)
-                key = ((unsigned long long)orderable(x) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)q);
+                key = ((unsigned long long)order_key(x) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)q);
         }
         const unsigned long long mask = __ballot(key != 0);
         int base = 0;
@@ -182,7 +162,7 @@ __global__ __launch_bounds__(64 * NW) void nms_class_kernel(const float *__restr
     int n2 = 64;
     while (n2 < n) n2 <<= 1;
     for (int i = n + tid; i < n2; i += NT) keys[i] = 0;
-    bitonic_desc<NT>(keys, n2);
+    bitonic_desc<NT>(keys, n2);                  // (its entry barrier orders the fill and the compaction before the sort)
     if (n == 0) return;
     const float off = (float)c * (ws.maxc[b] + 1.0f);
     for (int i = tid; i < n; i += NT) {
@@ -265,8 +245,7 @@ __global__ __launch_bounds__(64 * NW) void nms_class_kernel(const float *__restr
 
 // ---- per image: the max_num largest keys, sorted; decode and emit
 constexpr int kTopThreads = 1024, kTopCap = 2048;
-constexpr int kHistCopies = 64, kHistStride = 257;      // one histogram per lane id; the odd stride spreads a digit's
-                                                        // 64 copies over the 64 LDS banks (no same-address atomics)
+constexpr int kHistCopies = 64;                         // one histogram per lane id (select.h): no same-address atomics
 
 __global__ __launch_bounds__(kTopThreads) void nms_topk_kernel(const float *__restrict__ logits, int Q, int C,
                                                                int max_num, Workspace ws, float *__restrict__ dets,
@@ -276,7 +255,7 @@ __global__ __launch_bounds__(kTopThreads) void nms_topk_kernel(const float *__re
     __shared__ int hist[kHistCopies * kHistStride];
     __shared__ int bins[256];
     __shared__ int s_digit, s_remaining, s_matching, s_fill;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int K = ws.count[b];
     const unsigned long long *keys = ws.keys + (size_t)b * Q * C;
     const int nout = K < max_num ? K : max_num;
@@ -291,30 +270,10 @@ __global__ __launch_bounds__(kTopThreads) void nms_topk_kernel(const float *__re
         // not yet excluded fits the sort buffer the passes stop.
         unsigned long long prefix = 0, mask = 0;
         for (int pass = 7; pass >= 0; --pass) {
-            for (int i = tid; i < kHistCopies * kHistStride; i += kTopThreads) hist[i] = 0;
-            __syncthreads();
-            for (int i = tid; i < K; i += kTopThreads) {
-                const unsigned long long k = keys[i];
-                if ((k & mask) == prefix) atomicAdd(&hist[lane * kHistStride + (int)((k >> (8 * pass)) & 255)], 1);
-            }
-            __syncthreads();
-            if (tid < 256) {
-                int v = 0;
-                for (int cp = 0; cp < kHistCopies; ++cp) v += hist[cp * kHistStride + tid];
-                bins[tid] = v;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int rem = s_remaining, d = 255;
-                for (; d > 0; --d) {
-                    if (bins[d] >= rem) break;
-                    rem -= bins[d];
-                }
-                s_digit = d;
-                s_remaining = rem;
-                s_matching = bins[d];
-            }
-            __syncthreads();
+            semidetr::histogram_pass<kTopThreads, kHistCopies>(hist, keys, K, prefix, mask, pass);
+            // 1 <= s_remaining <= words counted: it starts as nout = max_num in [1, kTopCap] (launcher) against K > kTopCap
+            // words, and every pass leaves the rank inside the chosen digit, whose words are the next pass's
+            semidetr::pick_digit<kTopThreads, kHistCopies>(hist, bins, &s_digit, &s_remaining, &s_matching);
             prefix |= (unsigned long long)s_digit << (8 * pass);
             mask |= 0xFFull << (8 * pass);
             if ((nout - s_remaining) + s_matching <= kTopCap) break;        // uniform

@@ -15,13 +15,18 @@
 // The order (key descending, token ascending) is total, so the selection is deterministic where torch.topk's is not: all
 // padded tokens have bit-identical logits.
 #include "common.h"
+#include "select.h"
 
 namespace {
+
+using semidetr::kHistStride;
+using semidetr::order_key;
+using semidetr::sigmoidf_;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 64;                     // tokens per workgroup of the streaming kernels
 constexpr int kTopThreads = 1024;
-constexpr int kHistCopies = 16, kHistStride = 257;
+constexpr int kHistCopies = 16;
 constexpr size_t kLdsBudget = 160 * 1024 - 2048;      // dynamic LDS of the top-k kernel; the rest is its static part
 
 struct Levels {
@@ -36,8 +41,6 @@ __device__ inline void level_hw(const Levels &lv, int l, int S, int &H, int &W)
     if (h < 1 || w < 1 || h > S || w > S || h * w > S) h = w = 0;      // a level that cannot lie in S tokens: no tokens
     H = (int)h, W = (int)w;
 }
-
-__device__ inline float sigmoidf_(float x) { return __fdiv_rn(1.f, 1.f + expf(-x)); }
 
 // ---- anchors + masked memory.  grid (ceil(S / kTile), N)
 __global__ __launch_bounds__(kThreads) void qsel_proposals_kernel(const float *__restrict__ memory,
@@ -137,16 +140,8 @@ __global__ __launch_bounds__(kThreads) void qsel_mask_rows_kernel(const float *_
     }
 }
 
-// ---- key = max over the classes, as an integer that orders like the float: NaN (any sign) above +inf, -0 == +0
+// ---- key = max over the classes, as the integer that orders like the float (order_key, select.h)
 __device__ inline float max_nan(float m, float v) { return (m != m) ? m : ((v != v || v > m) ? v : m); }
-
-__device__ inline unsigned order_key(float v)
-{
-    if (v != v) return 0xFFFFFFFFu;
-    if (v == 0.f) v = 0.f;
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // 16 lanes per row, four rows per wavefront and pass.  grid ceil(rows / 16)
 __global__ __launch_bounds__(kThreads) void qsel_rowmax_kernel(const float *__restrict__ logits, int64_t rows, int C, int vec4,
@@ -185,7 +180,7 @@ __global__ __launch_bounds__(kTopThreads) void qsel_topk_kernel(const unsigned *
     unsigned long long *sel = qsel_smem;
     int *hist = reinterpret_cast<int *>(sel + kcap);
     unsigned *keys_l = reinterpret_cast<unsigned *>(hist + kHistCopies * kHistStride);
-    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = blockIdx.x, tid = threadIdx.x;
     const unsigned *kg = keys_g + (int64_t)n * S;
     int32_t *inv = inverse + (int64_t)n * S;
     for (int i = tid; i < S; i += kTopThreads) {
@@ -200,67 +195,20 @@ __global__ __launch_bounds__(kTopThreads) void qsel_topk_kernel(const unsigned *
     // number of tokens with exactly that key which belong to the selection
     unsigned prefix = 0, pmask = 0;
     for (int pass = 3; pass >= 0; --pass) {
-        for (int i = tid; i < kHistCopies * kHistStride; i += kTopThreads) hist[i] = 0;
-        __syncthreads();
-        for (int i = tid; i < S; i += kTopThreads) {
-            const unsigned u = keys[i];
-            if ((u & pmask) == prefix) atomicAdd(&hist[(lane & (kHistCopies - 1)) * kHistStride + (int)((u >> (8 * pass)) & 255)], 1);
-        }
-        __syncthreads();
-        if (tid < 256) {
-            int v = 0;
-            for (int cp = 0; cp < kHistCopies; ++cp) v += hist[cp * kHistStride + tid];
-            bins[tid] = v;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int rem = s_remaining, d = 255;
-            for (; d > 0; --d) {
-                if (bins[d] >= rem) break;
-                rem -= bins[d];
-            }
-            s_digit = d;
-            s_remaining = rem;
-        }
-        __syncthreads();
+        semidetr::histogram_pass<kTopThreads, kHistCopies>(hist, keys, S, prefix, pmask, pass);
+        // 1 <= s_remaining <= words counted: it starts as k in [1, S] (launcher) against all S keys, and every pass leaves the
+        // rank inside the chosen digit, whose keys are the next pass's
+        semidetr::pick_digit<kTopThreads, kHistCopies>(hist, bins, &s_digit, &s_remaining);
         prefix |= (unsigned)s_digit << (8 * pass);
         pmask |= 0xFFu << (8 * pass);
     }
     const int ties = s_remaining;
-    // collect: every key above the k-th, and the first `ties` tokens, in token order, that equal it
-    for (int i0 = 0; i0 < S; i0 += kTopThreads) {
-        const int i = i0 + tid;
-        const unsigned u = i < S ? keys[i] : 0u;
-        const bool above = i < S && u > prefix, tie = i < S && u == prefix;
-        const unsigned long long b = __ballot(tie);
-        if (lane == 0) s_wave[wave] = __popcll(b);
-        __syncthreads();
-        int before = s_base;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        const int rank = before + __popcll(b & ((1ull << lane) - 1ull));
-        if (above || (tie && rank < ties))
-            sel[atomicAdd(&s_fill, 1)] = ((unsigned long long)u << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
-        __syncthreads();
-        if (tid == 0) {
-            int t = 0;
-            for (int w = 0; w < kTopThreads / 64; ++w) t += s_wave[w];
-            s_base += t;
-        }
-        // (s_base / s_wave are rewritten only behind the next iteration's first barrier or read behind it)
-        __syncthreads();
-    }
-    // bitonic sort, descending, of the kcap slots (unused ones are 0 and sink to the end)
-    for (int size = 2; size <= kcap; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (kcap >> 1); t += kTopThreads) {
-                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                const bool desc = (lo & size) == 0;
-                const unsigned long long a = sel[lo], c = sel[hi];
-                if ((a < c) == desc) { sel[lo] = c; sel[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    // every key above the k-th and the first `ties` tokens, in token order, that equal it; then the kcap slots sorted (the
+    // unused ones are 0 and sink to the end)
+    semidetr::collect_with_ties<kTopThreads>(keys, S, prefix, ties, s_wave, &s_base, [&](int i, unsigned u) {
+        sel[atomicAdd(&s_fill, 1)] = ((unsigned long long)u << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
+    });
+    semidetr::bitonic_desc<kTopThreads>(sel, kcap);
     for (int r = tid; r < k; r += kTopThreads) {
         const unsigned i = 0xFFFFFFFFu - (unsigned)(sel[r] & 0xFFFFFFFFull);
         indices[(int64_t)n * k + r] = (int64_t)i;
@@ -371,33 +319,9 @@ int check_sizes(const char *what, int N, int S, int D)
     return SEMIDETR_OK;
 }
 
-int next_pow2(int v)
-{
-    int p = 2;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 size_t topk_lds_bytes(int S, int kcap, bool in_lds)
 {
     return (size_t)kcap * 8 + (size_t)kHistCopies * kHistStride * 4 + (in_lds ? (size_t)S * 4 : 0);
-}
-
-// dynamic LDS above 64 KB has to be allowed per kernel and per device
-int allow_topk_lds(size_t bytes)
-{
-    if (bytes <= 64 * 1024) return SEMIDETR_OK;
-    static thread_local size_t granted[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return semidetr::fail((int)e, "query_select topk: hipGetDevice: %s", hipGetErrorString(e));
-    if (dev >= 0 && dev < 64 && granted[dev] >= bytes) return SEMIDETR_OK;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&qsel_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kLdsBudget);
-    if (e != hipSuccess)
-        return semidetr::fail((int)e, "query_select topk: hipFuncSetAttribute(%zu bytes of LDS): %s", kLdsBudget, hipGetErrorString(e));
-    if (dev >= 0 && dev < 64) granted[dev] = kLdsBudget;
-    return SEMIDETR_OK;
 }
 
 }  // namespace
@@ -467,10 +391,11 @@ extern "C" int semidetr_qsel_topk_f32(void *stream, const float *logits, int N, 
                      semidetr_qsel_topk_workspace_bytes(N, S));
     const int64_t rows = (int64_t)N * S;
     unsigned *keys = static_cast<unsigned *>(workspace);
-    const int kcap = next_pow2(k);
+    const int kcap = semidetr::next_pow2(k);
     const bool in_lds = topk_lds_bytes(S, kcap, true) <= kLdsBudget;
     const size_t lds = topk_lds_bytes(S, kcap, in_lds);
-    if (int rc = allow_topk_lds(lds)) return rc;
+    if (lds > 64 * 1024)       // the fixed budget, not `lds`: one grant per device covers every later shape
+        if (int rc = semidetr::allow_big_lds(&qsel_topk_kernel, kLdsBudget, "query_select topk")) return rc;
     const int vec4 = C % 4 == 0 && aligned16(logits);
     hipLaunchKernelGGL(qsel_rowmax_kernel, dim3((unsigned)((rows + kThreads / 16 - 1) / (kThreads / 16))), dim3(kThreads), 0,
                        semidetr::as_stream(stream), logits, rows, C, vec4, keys);
