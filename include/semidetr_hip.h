@@ -654,6 +654,55 @@ int semidetr_det_decode_f32(void *stream, const float *cls_logits, const float *
                             int64_t *out_labels /* (B, k) */, float *out_dets_by_class /* (B, k, 5), nullable */,
                             int32_t *out_class_offsets /* (B, C + 1), nullable together */);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cross-view query consistency loss (ABI 7, additive): the last block of DinoDetrSSOD.unsup_loss, every decoder layer fused.
+ *
+ * Replaces  the `for layer_id in range(len(hs_v1))` loop   detr_ssod/models/dino_detr_ssod.py:472-481
+ *           (slice, two index gathers, two F.normalize, mse_loss, weights, mean, x 10 -- and their backward)
+ *
+ *   loss_l = scale * mean over (k, d) of  w_k (y1 - y2)_d^2,   y = x / max(||x||_2, eps),
+ *   x1 = hs_v1[l][bid_k, idx_k, :], x2 = hs_v2[l][bid_k, idx_k, :] (detached), k < K = num_known, d < D = dim.
+ *
+ * fp32, on `stream`, no host synchronisation, nothing read back, no memset, no float atomics; bitwise reproducible.
+ * The parameter block is read on the host during the call.  Per layer and view: a base pointer and the batch / query strides in
+ * ELEMENTS (the reference's hs[l] is a transposed view of a (Q, B, D) buffer); the last dimension has stride 1, every row
+ * starts 16-byte aligned (base aligned, strides multiples of 4).  D % 4 == 0; D == 256 is the tuned instantiation.
+ * known_bid is fp32 (what prepare_unsup_cdn produces) or int64 (bid_is_int64); loss_weights (K) may be NULL = all zero (past
+ * the warm-up).  The `[:, :pad_size]` slice is a bound: a pair with bid outside [0, batch) or idx outside [0, pad_size) is
+ * never dereferenced, it makes every layer's loss NaN and gets no gradient row.  The (bid, idx) pairs must be distinct.
+ *
+ * semidetr_consis_loss_forward_f32 -- two launches (rows -> fixed partial slots; one workgroup reduces them in index order
+ *   in fp64 and builds the inverse map (b, q) -> k in the workspace): losses (num_layers) =
+ *   (float)(sum_l * (double)(scale / (K * D))).
+ * semidetr_consis_loss_backward_f32 -- one launch; the workspace is the one the forward filled (same parameter block).
+ *   grad_losses (num_layers) upstream gradients; layer[l].grad_v1 the DENSE gradient (batch, num_query, D) contiguous of
+ *   hs_v1[l], every element written: selected rows get  g / n1 - x1 (x1 . g) / n1^3  with g = 2 c_k (y1 - y2),
+ *   c_k = scale w_k upstream_l / (K D)  (n1 < eps: g / eps, torch's clamp_min gate), all other rows zeros.
+ * workspace: semidetr_consis_loss_workspace_bytes(num_layers, num_known, batch, pad_size) bytes, 8-byte aligned (0 for sizes
+ *   outside the limits); no initialisation needed.
+ * Limits: num_layers <= SEMIDETR_CONSIS_MAX_LAYERS, batch * num_query < 2^27, num_known < 2^24.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_CONSIS_MAX_LAYERS 16
+typedef struct semidetr_consis_layer {
+    const float *v1, *v2;                      /* hs_v1[l], hs_v2[l] */
+    int64_t v1_stride[2], v2_stride[2];        /* (batch, query) strides in elements */
+    float *grad_v1;                            /* backward only: (batch, num_query, dim) contiguous */
+} semidetr_consis_layer;
+typedef struct semidetr_consis_loss {
+    int num_layers, batch, num_query, dim, pad_size, num_known;
+    int bid_is_int64;                          /* known_bid: 0 = float32, 1 = int64 */
+    float scale, eps;                          /* 10, 1e-12 in the reference */
+    const void *known_bid;                     /* (num_known) */
+    const int64_t *map_known_indice;           /* (num_known) */
+    const float *loss_weights;                 /* (num_known), NULL = zeros */
+    semidetr_consis_layer layer[SEMIDETR_CONSIS_MAX_LAYERS];
+} semidetr_consis_loss;
+size_t semidetr_consis_loss_workspace_bytes(int num_layers, int num_known, int batch, int pad_size);
+int semidetr_consis_loss_forward_f32(void *stream, const semidetr_consis_loss *params /* host */, void *workspace,
+                                     size_t workspace_bytes, float *losses);
+int semidetr_consis_loss_backward_f32(void *stream, const semidetr_consis_loss *params /* host */, const void *workspace,
+                                      size_t workspace_bytes, const float *grad_losses);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ from .set_loss import FocalLoss, SetLossSegment, loss_set, set_losses  # noqa: E
 from .dn_query import consistency_queries, prepare_for_cdn, prepare_for_cdn_plus, prepare_unsup_cdn  # noqa: E402,F401
 from .query_select import gen_encoder_output_proposals, select_queries, two_stage_queries  # noqa: E402,F401
 from .detect import PendingDetections, detection_results, get_bboxes  # noqa: E402,F401
+from .consis_loss import ConsistencyLossFunction, consistency_loss  # noqa: E402,F401
 from .pseudo_label import (filter_pseudo_labels, get_bboxes_for_pseudo_label, teacher_pseudo_labels,  # noqa: E402,F401
                            transform_bboxes)
 
@@ -38,4 +39,4 @@ __all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttn", 
            "fit_gmm_threshold_segments", "unsup_gmm_filter", "GmmFilterResult", "PendingGmmFilter",
            "FocalLoss", "SetLossSegment", "loss_set", "set_losses", "prepare_for_cdn", "prepare_for_cdn_plus",
            "prepare_unsup_cdn", "consistency_queries", "gen_encoder_output_proposals", "select_queries", "two_stage_queries",
-           "get_bboxes", "detection_results", "PendingDetections"]
+           "get_bboxes", "detection_results", "PendingDetections", "consistency_loss", "ConsistencyLossFunction"]

@@ -85,6 +85,10 @@ SIGNATURES = {
     # detection decode at evaluation / inference time (detect.py)
     "semidetr_det_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
     "semidetr_det_decode_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p, ctypes.c_size_t] + [c_void_p] * 4),
+    # cross-view consistency loss (consis_loss.py); the parameter block (semidetr_consis_loss, consis_loss._Params) is a host pointer
+    "semidetr_consis_loss_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
+    "semidetr_consis_loss_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "semidetr_consis_loss_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so
