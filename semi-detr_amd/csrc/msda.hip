@@ -75,7 +75,7 @@ constexpr int kMaxLevels = 32;
 #define SEMIDETR_SCATTER_WPE 6
 #endif
 #ifndef SEMIDETR_SCATTER_WU
-#define SEMIDETR_SCATTER_WU 8      // entries per stream and trip of the row walk (+ 1000: paired corners, msda_region.h)
+#define SEMIDETR_SCATTER_WU 8      // entries per stream and trip of the row walk (+ kWuPaired: paired corners, msda_region.h ScatterWu)
 #endif
 #ifndef SEMIDETR_SCATTER_NT
 #define SEMIDETR_SCATTER_NT 512    // (704 threads = one sample per thread, no half-empty second sample slot, two workgroups per CU:
@@ -124,24 +124,18 @@ constexpr int kMaxLevels = 32;
 #define SEMIDETR_RW_DBG 0        // timing aids of the four-level msda_rw_d32 (results wrong), tuning builds only: see msda_rw.h
 #endif
 #ifndef SEMIDETR_RW_TUNE
-#define SEMIDETR_RW_TUNE 98320   // (round 5: + 6400 level constants from an LDS table, + 12800 region query list in LDS, + 25600 compact records for
-                                 //  out-of-window samples, + 400 one such sample per octet and trip -- the geometry of a round 284 -> ~130 VALU
-                                 //  instructions, no publish step: probe (tools/r05_ab_fwd.sh, medians of 5) 169.1 -> 164.4 us at sigma 1 px,
-                                 //  179.4 -> 172.7 at 2 px, 202.3 -> 190.1 at 3 px; + 51200 window offsets as two 32-bit byte offsets: another -1 %)
-                                 // 1920 = msda_rw_d32: 10 x compute-loop samples between scheduling barriers (two: with four samples' LDS reads
-                                 // in flight round 4's first version spilled; one: 2 us slower) + 100: one level-0 sample's corner loads in
-                                 // flight instead of two (-33 VGPRs) + 200: level constants re-selected where they are used and staging
-                                 // coordinates rebuilt per region instead of living in registers (256 -> 160 VGPRs: what lets 768 threads run)
-                                 // + 1600: the fused prologue's location arithmetic at the start of the round that uses the loaded data, not
-                                 // where the loads are issued (a round early, waiting for them): fused-prologue forward 189.8 -> 188.0 us
+#define SEMIDETR_RW_TUNE kRwProduct4        // msda_rw_d32's configuration: msda_rw.h's rw_tune(named flags, samples between scheduling barriers).  The product's
+                                            // are defined, pinned to their historical numbers and explained at kRwProduct4 / kRwProduct5 below; a tuning build
+                                            // may pass an archived record's plain integer instead (tools/ab_build.sh -DSEMIDETR_RW_TUNE=1920)
 #endif
 #ifndef SEMIDETR_RW_SB_LOCATTN
-#define SEMIDETR_RW_SB_LOCATTN 0      // added to SEMIDETR_RW_TUNE for the reference contract: 10 x (samples between barriers - 2).  Round 5: 20 (four
-                                      // samples: -1.3 ... -2 %); round 6, with the branch-free round loop (msda_rw.h SEMIDETR_BRFREE; 129 VGPRs at any spacing):
+#define SEMIDETR_RW_SB_LOCATTN rw_untune(SEMIDETR_RW_TUNE).samples_per_barrier
+                                      // the reference contract's compute-loop samples between scheduling barriers (the fused prologue keeps SEMIDETR_RW_TUNE's).
+                                      // Round 5: four (-1.3 ... -2 %); round 6, with the branch-free round loop (msda_rw.h SEMIDETR_BRFREE; 129 VGPRs at any spacing):
                                       // two / three / four samples 162.5-163.8 / 168.5-171.0 / 164.3-165.4 us (tools/r05_ab_kern.sh, same box) -> two, like RawIO
 #endif
 #ifndef SEMIDETR_RW_TUNE_MASK
-#define SEMIDETR_RW_TUNE_MASK 98320   // the instantiation with the padding mask (166 VGPRs; with the table but without the compact records it spills)
+#define SEMIDETR_RW_TUNE_MASK kRwProduct4   // the instantiation with the padding mask (166 VGPRs; with the table but without the compact records it spills)
 #endif
 #ifndef SEMIDETR_RW_RTH
 #define SEMIDETR_RW_RTH 25       // msda_rw_d32, four levels: LARGEST region height (x 16 columns; the grid is tiled evenly, msda_rw.h) and coarse-level
@@ -160,17 +154,12 @@ constexpr int kMaxLevels = 32;
 #define SEMIDETR_RW_NT5 960      // ... the five-level instantiation: margin 4 is what fits either way; 24 x 16 regions like the four-level one, and the
                                  //     largest workgroup that fits beside their windows: 15 waves (16 x 16 / 1024 threads: 202 / 209 / 243 us at sigma 1 /
                                  //     2 / 3 px, 24 x 16 / 960: 195 / 204 / 241, / 896: 190 / 204 / 242)
-#define SEMIDETR_RW_TUNE5 47910  // (round 5: as four levels -- split loads, level table, query list, compact records, one out-of-window sample per trip;
-                                 //  the wide window offsets do not fit beside 120 octets' records.  The fused prologue keeps round 4's configuration (with table +
-                                 //  query list it spills at 128 registers): SEMIDETR_RW_TUNE5_RAW / _MASK)
+#define SEMIDETR_RW_TUNE5 kRwProduct5   // (the fused prologue kept round 4's configuration through round 5 -- with table + query list it spilled at 128
+                                        //  registers: SEMIDETR_RW_TUNE5_RAW / _MASK)
 #ifndef SEMIDETR_RW_TUNE5_RAW
-#define SEMIDETR_RW_TUNE5_RAW 47910      // (round 6: with no branch around the round loop's loads -- msda_rw.h SEMIDETR_BRFREE -- the fused prologue's five-level
-#define SEMIDETR_RW_TUNE5_MASK 47910     //  instantiations fit the table / list / compact-record configuration too: 112 / 113 VGPRs, no spill; rounds 4-5: 1110)
-#endif
-                                 // 1110 =     (16 waves per CU, 128 VGPRs): ONE sample between scheduling barriers (three passes of samples per lane) and
-                                 //     + 800: everything derived from the thread index rebuilt per round / region.  768 threads: 223 / 232 / 273 us
-                                 //     at sigma 1 / 2 / 3 px, 1024: 208 / 225 / 255.  (Four levels at 1024 threads would have to give up margin 6
-                                 //     for 5: 206 against 205 us -- no gain.)
+#define SEMIDETR_RW_TUNE5_RAW kRwProduct5      // (round 6: with no branch around the round loop's loads -- msda_rw.h SEMIDETR_BRFREE -- the fused prologue's five-level
+#define SEMIDETR_RW_TUNE5_MASK kRwProduct5     //  instantiations fit the table / list / compact-record configuration too: 112 / 113 VGPRs, no spill; rounds 4-5:
+#endif                                         //  rw_tune(kRwRebuildTid | kRwLean | kRwOneFine, 1) = 1110)
 #endif
 
 // ---------------------------------------------------------------------------------------------
@@ -620,6 +609,55 @@ bool slot_samples_are_near(int slot_id)
     return sl.updates > 0 && sl.last_frac >= 0.f && sl.last_frac < kFarToWindowGather;
 }
 
+// ---- the product configurations of the region-window forward (msda_rw.h; defaults of SEMIDETR_RW_TUNE... above).  The numbers they are
+//      pinned to are what DESIGN.md, profiles/ and the archived A/B scripts quote (kernel names print them).
+// Four levels.  Round 4 (1920): two compute-loop samples between scheduling barriers (with four samples' LDS reads in flight round 4's first
+// version spilled; one: 2 us slower); kRwOneFine -33 VGPRs; kRwLean 256 -> 160 VGPRs: what lets 768 threads run; kRwSplitLoad: the fused
+// prologue's location arithmetic at the start of the round that uses the loaded data, not where the loads are issued (a round early, waiting for
+// them): fused-prologue forward 189.8 -> 188.0 us.  Round 5: kRwLevelTable, kRwQueryList, kRwCompact and kRwOneOowPerTrip -- the geometry of a
+// round 284 -> ~130 VALU instructions, no publish step: probe (tools/r05_ab_fwd.sh, medians of 5) 169.1 -> 164.4 us at sigma 1 px, 179.4 ->
+// 172.7 at 2 px, 202.3 -> 190.1 at 3 px; kRwWideOffsets: another -1 %.
+constexpr int kRwProduct4 = rw_tune(kRwWideOffsets | kRwCompact | kRwQueryList | kRwLevelTable | kRwSplitLoad | kRwOneOowPerTrip | kRwLean | kRwOneFine, 2);
+// Five levels.  Round 4 (1110; 16 waves per CU, 128 VGPRs): ONE sample between scheduling barriers (three passes of samples per lane) and
+// kRwRebuildTid.  768 threads: 223 / 232 / 273 us at sigma 1 / 2 / 3 px, 1024: 208 / 225 / 255.  (Four levels at 1024 threads would have to
+// give up margin 6 for 5: 206 against 205 us -- no gain.)  Round 5: as four levels -- split loads, level table, query list, compact records,
+// one out-of-window sample per trip; the wide window offsets do not fit beside 120 octets' records.
+constexpr int kRwProduct5 = rw_tune(kRwCompact | kRwQueryList | kRwLevelTable | kRwSplitLoad | kRwRebuildTid | kRwOneOowPerTrip | kRwLean | kRwOneFine, 1);
+static_assert(kRwProduct4 == 98320 && kRwProduct5 == 47910, "the product configurations keep their historical numbers");
+static_assert(rw_tune_or(kRwProduct4, kRwTailSplit) == 200720, "... and the tail-split variant its own (98320 + 100 x kRwTailSplit)");
+
+// One product configuration of the window forward, keyed on (IO, levels, padding mask): kernel, tail-split kernel, LDS bytes, threads and
+// region pixels all come from the ONE parameter set below, so what is launched and what it is given cannot disagree.
+// Level 0 through global loads, windows of the coarse levels with the widest margin that fits beside the octet records: one workgroup per CU
+// either way, and the workgroup as large as its registers allow (SEMIDETR_RW_NT).
+//   four levels: 24 x 16 regions, margin FIVE, 113 KB of windows + 34.5 KB of records (16 x 16 regions at margin 4 / 5 / 6 and
+//                sigma 2 px: 239 / 231 / 219-229 us, at 3 px: 290 / 265 / 252 us with 512 threads; SEMIDETR_RW_RTH above)
+//   five levels: 24 x 16 regions, margin FOUR (102 + 53 KB; margin 5 fits only a 640-thread workgroup), 960 threads; patch
+//                kernel 314 / 292 / 299 us at sigma 1 / 2 / 3 px, this one 195 / 204 / 241
+template <typename IO, int KL, bool MASK>
+struct RwProduct {
+    static constexpr bool kRaw = std::is_same<IO, RawIO>::value;
+    static_assert((KL == 4 || KL == 5) && (!MASK || kRaw), "four or five levels; the padding mask comes with the fused prologue");
+    static constexpr int threads = KL == 4 ? SEMIDETR_RW_NT : SEMIDETR_RW_NT5, rth = KL == 4 ? SEMIDETR_RW_RTH : SEMIDETR_RW_RTH5, rtw = 16;
+    static constexpr int hc = KL == 4 ? SEMIDETR_RW_HC : 4, dbg = KL == 4 ? SEMIDETR_RW_DBG : 0, region_px = rth * rtw;
+    // (the reference contract's four-level instantiation has its own barrier spacing, SEMIDETR_RW_SB_LOCATTN; the tail split, a four-level
+    //  instantiation of its own -- msda_rw.h kRwTailSplit --, keeps the configuration's)
+    static constexpr int tune4 = MASK ? SEMIDETR_RW_TUNE_MASK : SEMIDETR_RW_TUNE;
+    static constexpr int tune5 = MASK ? SEMIDETR_RW_TUNE5_MASK : (kRaw ? SEMIDETR_RW_TUNE5_RAW : SEMIDETR_RW_TUNE5);
+    static constexpr int tune = KL == 5 ? tune5 : (kRaw ? tune4 : rw_tune_spaced(tune4, SEMIDETR_RW_SB_LOCATTN));
+    static constexpr int tune_tail = rw_tune_or(tune4, kRwTailSplit);
+    template <int TUNE> static constexpr auto kernel_of = &msda_rw_d32<IO, threads, rth, rtw, -1, hc, KL, false, dbg, TUNE, MASK>;
+    template <int TUNE> static constexpr size_t lds_of = rw_lds_bytes<threads, rth, rtw, -1, hc, KL, TUNE>();
+    static constexpr auto kernel = kernel_of<tune>;
+    static constexpr decltype(kernel) kernel_tail = [] {      // null: this configuration has none
+        if constexpr (KL == 4) return kernel_of<tune_tail>;
+        else return decltype(kernel){nullptr};
+    }();
+    static constexpr size_t lds_bytes = lds_of<tune>;
+    static_assert(lds_bytes <= 160 * 1024, "region-window configuration does not fit the LDS");
+    static_assert(kernel_tail == nullptr || lds_of<tune_tail> == lds_bytes, "the tail-split instantiation is launched with the same LDS size");
+};
+
 // ---- product dispatch of the fast path (fp32, channels == 32), shared by the reference contract (LocAttnIO) and the
 //      fused prologue (RawIO).  Apart from the forward-kernel choice above, what runs is a function of the arguments only.
 template <typename IO>
@@ -648,14 +686,13 @@ int launch_fast_forward(hipStream_t st, const float *value, const int64_t *spati
         if (int rc = fwd_adapt_next(st, window_ok, (flags >> 8) & 0xff, L, fs, use_window)) return rc;
         if (use_window) {
             bool fell_back = false;      // a device / runtime that does not grant the window kernel its ~150 KB of LDS gets the patch kernel, not an error
-            // level 0 through global loads, windows of the coarse levels with the widest margin that fits beside the
-            // octet records: one workgroup per CU either way, and the workgroup as large as its registers allow (SEMIDETR_RW_NT).
-            //   four levels: 24 x 16 regions, margin FIVE, 113 KB of windows + 34.5 KB of records (16 x 16 regions at margin 4 / 5 / 6 and
-            //                sigma 2 px: 239 / 231 / 219-229 us, at 3 px: 290 / 265 / 252 us with 512 threads; SEMIDETR_RW_RTH above)
-            //   five levels: 24 x 16 regions, margin FOUR (102 + 53 KB; margin 5 fits only a 640-thread workgroup), 960 threads; patch
-            //                kernel 314 / 292 / 299 us at sigma 1 / 2 / 3 px, this one 195 / 204 / 241
-            // kern_tail: the same configuration with the tail split compiled in (TUNE + 102400; null: this configuration has none)
-            auto launch_window = [&](auto kern, decltype(kern) kern_tail, size_t wlds, int threads, int region_px) -> int {
+            // cfg: the RwProduct to run.  Its kernel_tail is the same configuration with the tail split compiled in (null: it has none)
+            auto launch_window = [&](auto cfg) -> int {
+                using C = decltype(cfg);
+                auto kern = C::kernel;
+                const auto kern_tail = C::kernel_tail;
+                constexpr size_t wlds = C::lds_bytes;
+                constexpr int threads = C::threads, region_px = C::region_px;
                 // grid sizing hint: the finest level of a DETR pyramid holds ~3/4 of the pixels; a workgroup takes regions slot,
                 // slot + bound, ... so any bound >= 1 is correct (the level table lives in device memory)
                 const int wbound = ((S * 3 / 4 + region_px - 1) / region_px) * 9 / 8 + 2 * L;
@@ -677,32 +714,10 @@ int launch_fast_forward(hipStream_t st, const float *value, const int64_t *spati
                 return semidetr::launch_status("msda_rw_d32<forward>");
             };
             auto pick_window = [&]() -> int {
-                constexpr int kTune5 = std::is_same<IO, RawIO>::value ? SEMIDETR_RW_TUNE5_RAW : SEMIDETR_RW_TUNE5;
-                // (the reference contract's main instantiation has the registers for THREE (round 5: four) samples between scheduling barriers since the
-                //  compact records -- 168 VGPRs, no spill: -1.3 ... -2 % in the probe; the fused prologue's and the tail-split ones spill there)
-                constexpr int kTune4 = std::is_same<IO, RawIO>::value ? SEMIDETR_RW_TUNE : SEMIDETR_RW_TUNE + SEMIDETR_RW_SB_LOCATTN;
-                constexpr size_t wlds4 = rw_lds_bytes<SEMIDETR_RW_NT, SEMIDETR_RW_RTH, 16, -1, SEMIDETR_RW_HC, 4, SEMIDETR_RW_TUNE>(), wlds5 = rw_lds_bytes<SEMIDETR_RW_NT5, SEMIDETR_RW_RTH5, 16, -1, 4, 5, kTune5>();
-                static_assert(wlds4 <= 160 * 1024 && wlds5 <= 160 * 1024, "region-window configuration does not fit the LDS");
                 if constexpr (std::is_same<IO, RawIO>::value) {
-                    if (io.has_mask()) {
-                        if (L == 4) {
-                            constexpr size_t wlds4m = rw_lds_bytes<SEMIDETR_RW_NT, SEMIDETR_RW_RTH, 16, -1, SEMIDETR_RW_HC, 4, SEMIDETR_RW_TUNE_MASK>();
-                            static_assert(wlds4m <= 160 * 1024, "region-window configuration does not fit the LDS");
-                            return launch_window(&msda_rw_d32<IO, SEMIDETR_RW_NT, SEMIDETR_RW_RTH, 16, -1, SEMIDETR_RW_HC, 4, false, SEMIDETR_RW_DBG, SEMIDETR_RW_TUNE_MASK, true>,
-                                                 &msda_rw_d32<IO, SEMIDETR_RW_NT, SEMIDETR_RW_RTH, 16, -1, SEMIDETR_RW_HC, 4, false, SEMIDETR_RW_DBG, SEMIDETR_RW_TUNE_MASK + 102400, true>,
-                                                 wlds4m, SEMIDETR_RW_NT, SEMIDETR_RW_RTH * 16);
-                        }
-                        constexpr size_t wlds5m = rw_lds_bytes<SEMIDETR_RW_NT5, SEMIDETR_RW_RTH5, 16, -1, 4, 5, SEMIDETR_RW_TUNE5_MASK>();
-                        return launch_window(&msda_rw_d32<IO, SEMIDETR_RW_NT5, SEMIDETR_RW_RTH5, 16, -1, 4, 5, false, 0, SEMIDETR_RW_TUNE5_MASK, true>, nullptr, wlds5m,
-                                             SEMIDETR_RW_NT5, SEMIDETR_RW_RTH5 * 16);
-                    }
+                    if (io.has_mask()) return L == 4 ? launch_window(RwProduct<IO, 4, true>{}) : launch_window(RwProduct<IO, 5, true>{});
                 }
-                if (L == 4)
-                    return launch_window(&msda_rw_d32<IO, SEMIDETR_RW_NT, SEMIDETR_RW_RTH, 16, -1, SEMIDETR_RW_HC, 4, false, SEMIDETR_RW_DBG, kTune4>,
-                                         &msda_rw_d32<IO, SEMIDETR_RW_NT, SEMIDETR_RW_RTH, 16, -1, SEMIDETR_RW_HC, 4, false, SEMIDETR_RW_DBG, SEMIDETR_RW_TUNE + 102400>, wlds4,
-                                         SEMIDETR_RW_NT, SEMIDETR_RW_RTH * 16);
-                return launch_window(&msda_rw_d32<IO, SEMIDETR_RW_NT5, SEMIDETR_RW_RTH5, 16, -1, 4, 5, false, 0, kTune5>, nullptr, wlds5, SEMIDETR_RW_NT5,
-                                     SEMIDETR_RW_RTH5 * 16);
+                return L == 4 ? launch_window(RwProduct<IO, 4, false>{}) : launch_window(RwProduct<IO, 5, false>{});
             };
             const int wrc = pick_window();
             if (!fell_back) return wrc;
@@ -713,7 +728,7 @@ int launch_fast_forward(hipStream_t st, const float *value, const int64_t *spati
         // included); a workgroup takes patches slot, slot + hint, ... so any hint >= 1 is correct
         const int bound = (S + 31) / 32 * 5 / 4 + 4 * L;
         SEMIDETR_REQUIRE((int64_t)N * bound * M < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_forward: grid too large");
-        hipLaunchKernelGGL((msda_fwd_d32<1, 4, 408, IO>), dim3((unsigned)((int64_t)N * bound * M)), dim3(256),
+        hipLaunchKernelGGL((msda_fwd_d32<1, 4, patch_hw(4, 8), IO>), dim3((unsigned)((int64_t)N * bound * M)), dim3(256),
                            (size_t)32 * (L * P + 1) * 32, st, value, spatial_shapes, level_start, io, S, M, L, Lq, P, bound, out, fs);
         g_last_kernels = "msda_fwd_d32<1, 4, 408";
         return semidetr::launch_status("msda_fwd_d32<patch>");
@@ -809,14 +824,14 @@ int launch_fast_backward(hipStream_t st, const float *grad_out, const float *val
         }
         if (window_gather) {
         } else if (L * P == 16)             // DINO: sample loop unrolled, results in registers
-            hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, 408, SEMIDETR_GATHER_WPE, SEMIDETR_GATHER_KB>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds, st,
+            hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8), SEMIDETR_GATHER_WPE, SEMIDETR_GATHER_KB>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds, st,
                                grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound, zero, (int64_t)(fill / 16));
         else if (L * P == 20)        // five levels (COCO-Full recipe)
         {
             // (the fused prologue's instantiation holds its softmax / location arithmetic besides: with 16 corner loads in flight it
             //  spills at four waves per SIMD since it also carries the padding mask's summary -- 8 in flight: 98 registers)
             constexpr int kb5 = std::is_same<IO, RawIO>::value ? 2 : SEMIDETR_GATHER5_KB;
-            hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 20, 408, SEMIDETR_GATHER5_WPE, kb5>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds, st,
+            hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 20, patch_hw(4, 8), SEMIDETR_GATHER5_WPE, kb5>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds, st,
                                grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound, zero, (int64_t)(fill / 16));
         }
         else

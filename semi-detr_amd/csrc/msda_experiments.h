@@ -10,7 +10,7 @@ std::atomic<int> g_fwd_variant_a{0}, g_bwd_variant_a{0};
 #define g_bwd_variant (g_bwd_variant_a.load(std::memory_order_relaxed))
 
 // ---- region-window kernels (msda_rw.h): one launcher for the forward and the gather -------------------------------
-template <typename IO, int NT, int RTH, int RTW, int H0, int HC, int KL, bool GATHER, int DBG = 0, int TUNE = 42>
+template <typename IO, int NT, int RTH, int RTW, int H0, int HC, int KL, bool GATHER, int DBG = 0, int TUNE = rw_tune(0, 4, 2)>
 int launch_rw(hipStream_t st, const float *grad_out, const float *value, const int64_t *spatial_shapes,
               const int64_t *level_start, const IO &io, int N, int S, int M, float *out, float4 *zero, int64_t zero_n4)
 {
@@ -34,77 +34,79 @@ template <typename IO, int KL, bool GATHER>
 int launch_rw_cfg(int cfg, hipStream_t st, const float *grad_out, const float *value, const int64_t *spatial_shapes,
                   const int64_t *level_start, const IO &io, int N, int S, int M, float *out, float4 *zero, int64_t zero_n4)
 {
-#define RW(NT_, RH_, RW_, H0_, HC_) RWT(NT_, RH_, RW_, H0_, HC_, 0, 42)
+#define RW(NT_, RH_, RW_, H0_, HC_) RWT(NT_, RH_, RW_, H0_, HC_, 0, rw_tune(0, 4, 2))
 #define RWT(NT_, RH_, RW_, H0_, HC_, DBG_, TUNE_) \
     launch_rw<IO, NT_, RH_, RW_, H0_, HC_, KL, GATHER, DBG_, TUNE_>(st, grad_out, value, spatial_shapes, level_start, io, N, S, M, out, zero, zero_n4)
+    // (the last argument: msda_rw.h's TUNE = rw_tune(flags, samples between scheduling barriers, pre-issued out-of-window samples))
+    constexpr int kLeanFine = kRwLean | kRwOneFine, kRound4 = kRwSplitLoad | kLeanFine;      // round 4's product flags: TUNE 1920
     if constexpr (KL == 4) {
         switch (cfg) {
-        case 0: return RWT(512, 8, 16, 4, 5, 0, 40);
-        case 1: if constexpr (!GATHER) return RWT(256, 16, 16, -1, 4, 0, 40); else return RWT(512, 8, 16, 4, 5, 0, 20);      // gather: a sample per scheduling barrier
-        case 2: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 0, 40); else return RWT(512, 8, 16, 4, 4, 0, 20);
-        case 3: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 3, 0, 40); else return RWT(512, 8, 16, 4, 5, 0, 60);
-        case 4: if constexpr (!GATHER) return RWT(256, 8, 8, -1, 4, 0, 40); else return RWT(768, 24, 16, -1, 5, 0, 1920);      // gather: the forward's product shape (level 0 through global loads)
-        case 5: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 4, 0, 40); else return RWT(768, 24, 16, -1, 5, 0, 2720);      // level 0 through global loads; gather: everything thread-derived rebuilt
-        case 6: if constexpr (!GATHER) return RWT(512, 8, 16, -1, 5, 0, 40); else return RWT(768, 16, 16, -1, 6, 0, 1920);
-        case 15: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 5, 0, 40); else break;      // the product's shape with margin 5 (134 KB of LDS)
-        case 16: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, 40); else break;      // margin 6: 159 KB of LDS
-        case 17: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 5, 1, 40); else break;      // ... instrumented
-        case 18: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, 20); else break;      // round 4's first product configuration (512 threads)
-        case 19: if constexpr (!GATHER) return RWT(256, 16, 16, -1, 6, 0, 20); else break;      // ... with 256-thread workgroups
+        case 0: return RWT(512, 8, 16, 4, 5, 0, rw_tune(0, 4));
+        case 1: if constexpr (!GATHER) return RWT(256, 16, 16, -1, 4, 0, rw_tune(0, 4)); else return RWT(512, 8, 16, 4, 5, 0, rw_tune(0, 2));      // gather: a sample per scheduling barrier
+        case 2: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 0, rw_tune(0, 4)); else return RWT(512, 8, 16, 4, 4, 0, rw_tune(0, 2));
+        case 3: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 3, 0, rw_tune(0, 4)); else return RWT(512, 8, 16, 4, 5, 0, rw_tune(0, 6));
+        case 4: if constexpr (!GATHER) return RWT(256, 8, 8, -1, 4, 0, rw_tune(0, 4)); else return RWT(768, 24, 16, -1, 5, 0, rw_tune(kRound4, 2));      // gather: the forward's product shape (level 0 through global loads)
+        case 5: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 4, 0, rw_tune(0, 4)); else return RWT(768, 24, 16, -1, 5, 0, rw_tune(kRound4 | kRwRebuildTid, 2));      // level 0 through global loads; gather: everything thread-derived rebuilt
+        case 6: if constexpr (!GATHER) return RWT(512, 8, 16, -1, 5, 0, rw_tune(0, 4)); else return RWT(768, 16, 16, -1, 6, 0, rw_tune(kRound4, 2));
+        case 15: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 5, 0, rw_tune(0, 4)); else break;      // the product's shape with margin 5 (134 KB of LDS)
+        case 16: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, rw_tune(0, 4)); else break;      // margin 6: 159 KB of LDS
+        case 17: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 5, 1, rw_tune(0, 4)); else break;      // ... instrumented
+        case 18: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, rw_tune(0, 2)); else break;      // round 4's first product configuration (512 threads)
+        case 19: if constexpr (!GATHER) return RWT(256, 16, 16, -1, 6, 0, rw_tune(0, 2)); else break;      // ... with 256-thread workgroups
         // round 4, second look: does the kernel want more waves?  1024-thread workgroups = 16 waves per CU (128 VGPRs); their octet
         // records take 66 KB, so the margin drops to 4 -- compared at equal margin (730 = 512 threads)
-        // TUNE + 100: one level-0 sample in flight instead of two; + 200: lean registers (level constants re-selected where they
+        // kRwOneFine: one level-0 sample in flight instead of two; kRwLean: lean registers (level constants re-selected where they
         // are used, staging coordinates rebuilt per region) -- 160 instead of 256 VGPRs, which is what lets a 768-thread workgroup run
-        case 30: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 0, 20); else break;
-        case 31: if constexpr (!GATHER) return RWT(1024, 16, 16, -1, 5, 0, 1120); else break;    // + 800: everything thread-derived rebuilt per round / region: 125 VGPRs
-        case 40: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, 1120); else break;
-        case 41: if constexpr (!GATHER) return RWT(1024, 16, 16, -1, 5, 0, 1110); else break;
-        case 42: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, 5120); else break;     // + 3200: window addresses by v_mad_u32_u16, FMAs with explicit op_sel
-        case 43: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, 1920); else break;     // the product configuration (= 734 + 1600)
-        case 44: if constexpr (!GATHER) return RWT(704, 16, 16, -1, 6, 0, 1920); else break;     // 11 waves: a region's 340 queries fill 3.86 rounds of 88
-        case 45: if constexpr (!GATHER) return RWT(768, 16, 32, -1, 4, 0, 1920); else break;     // 16 x 32 regions: 680 queries = 7.1 rounds, 1.2 instead of 2.9 staged rows per query; margin 4
-        case 46: if constexpr (!GATHER) return RWT(704, 16, 32, -1, 5, 0, 1920); else break;     // ... margin 5 fits beside 88 octets' records
-        case 47: if constexpr (!GATHER) return RWT(768, 32, 16, -1, 4, 0, 1920); else break;
-        case 48: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 0, 1920); else break;     // the PRODUCT configuration: 24 x 16 regions, 510 queries = 5.3 rounds, margin 5
-        case 49: if constexpr (!GATHER) return RWT(704, 32, 16, -1, 5, 0, 1920); else break;
-        case 51: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 0, 1921); else break;     // + ONE out-of-window sample per octet pre-issued before the LDS loop
-        case 52: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 0, 2721); else break;
-        case 53: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 0, 2722); else break;
-        case 54: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 1, 2721); else break;     // ... instrumented
-        case 55: if constexpr (!GATHER) return RWT(768, 22, 16, -1, 5, 0, 1920); else break;     // region heights by how evenly their queries fill rounds of 96: 22 rows = 4.87
-        case 56: if constexpr (!GATHER) return RWT(768, 25, 16, -1, 5, 0, 1920); else break;     // 25 rows = 5.53 (and four region rows exactly on a 100-row level)
-        case 57: if constexpr (!GATHER) return RWT(768, 20, 16, -1, 5, 0, 1920); else break;     // 20 rows = 4.43
-        case 50: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 1, 1920); else break;     // the product configuration, instrumented (tools/archive/r03_rw_dbg.py 750)
-        case 32: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, 220); else break;      // the product shape, lean
-        case 33: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, 240); else break;      // ... four samples between barriers again
-        case 34: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, 320); else break;      // the PRODUCT configuration: 12 waves per CU, margin 6
-        case 35: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, 310); else break;
-        case 36: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 5, 0, 320); else break;
-        case 37: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, 320); else break;
-        case 38: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, 340); else break;
-        case 39: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, 120); else break;
-        case 12: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 1, 40); else break;      // the PRODUCT configuration (702), instrumented
-        case 13: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 2, 40); else break;      // ... windows not staged (timing aid)
-        case 14: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 3, 40); else break;      // ... LDS loop skipped (timing aid)
-        case 7: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 4, 1, 40); else return RWT(512, 8, 16, 4, 5, 1, 40);
-        case 8: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 4, 2, 40); else return RWT(512, 8, 16, 4, 5, 2, 40);
-        case 9: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 4, 3, 40); else return RWT(512, 8, 16, 4, 5, 3, 40);
+        case 30: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 0, rw_tune(0, 2)); else break;
+        case 31: if constexpr (!GATHER) return RWT(1024, 16, 16, -1, 5, 0, rw_tune(kLeanFine | kRwRebuildTid, 2)); else break;    // kRwRebuildTid: everything thread-derived rebuilt per round / region: 125 VGPRs
+        case 40: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, rw_tune(kLeanFine | kRwRebuildTid, 2)); else break;
+        case 41: if constexpr (!GATHER) return RWT(1024, 16, 16, -1, 5, 0, rw_tune(kLeanFine | kRwRebuildTid, 1)); else break;
+        case 42: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, rw_tune(kRound4 | kRwMadU16, 2)); else break;     // kRwMadU16: window addresses by v_mad_u32_u16, FMAs with explicit op_sel
+        case 43: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, rw_tune(kRound4, 2)); else break;     // the product configuration (= 734 + kRwSplitLoad)
+        case 44: if constexpr (!GATHER) return RWT(704, 16, 16, -1, 6, 0, rw_tune(kRound4, 2)); else break;     // 11 waves: a region's 340 queries fill 3.86 rounds of 88
+        case 45: if constexpr (!GATHER) return RWT(768, 16, 32, -1, 4, 0, rw_tune(kRound4, 2)); else break;     // 16 x 32 regions: 680 queries = 7.1 rounds, 1.2 instead of 2.9 staged rows per query; margin 4
+        case 46: if constexpr (!GATHER) return RWT(704, 16, 32, -1, 5, 0, rw_tune(kRound4, 2)); else break;     // ... margin 5 fits beside 88 octets' records
+        case 47: if constexpr (!GATHER) return RWT(768, 32, 16, -1, 4, 0, rw_tune(kRound4, 2)); else break;
+        case 48: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 0, rw_tune(kRound4, 2)); else break;     // the PRODUCT configuration: 24 x 16 regions, 510 queries = 5.3 rounds, margin 5
+        case 49: if constexpr (!GATHER) return RWT(704, 32, 16, -1, 5, 0, rw_tune(kRound4, 2)); else break;
+        case 51: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 0, rw_tune(kRound4, 2, 1)); else break;     // + ONE out-of-window sample per octet pre-issued before the LDS loop
+        case 52: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 0, rw_tune(kRound4 | kRwRebuildTid, 2, 1)); else break;
+        case 53: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 0, rw_tune(kRound4 | kRwRebuildTid, 2, 2)); else break;
+        case 54: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 1, rw_tune(kRound4 | kRwRebuildTid, 2, 1)); else break;     // ... instrumented
+        case 55: if constexpr (!GATHER) return RWT(768, 22, 16, -1, 5, 0, rw_tune(kRound4, 2)); else break;     // region heights by how evenly their queries fill rounds of 96: 22 rows = 4.87
+        case 56: if constexpr (!GATHER) return RWT(768, 25, 16, -1, 5, 0, rw_tune(kRound4, 2)); else break;     // 25 rows = 5.53 (and four region rows exactly on a 100-row level)
+        case 57: if constexpr (!GATHER) return RWT(768, 20, 16, -1, 5, 0, rw_tune(kRound4, 2)); else break;     // 20 rows = 4.43
+        case 50: if constexpr (!GATHER) return RWT(768, 24, 16, -1, 5, 1, rw_tune(kRound4, 2)); else break;     // the product configuration, instrumented (tools/archive/r03_rw_dbg.py 750)
+        case 32: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, rw_tune(kRwLean, 2)); else break;      // the product shape, lean
+        case 33: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, rw_tune(kRwLean, 4)); else break;      // ... four samples between barriers again
+        case 34: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, rw_tune(kLeanFine, 2)); else break;      // the PRODUCT configuration: 12 waves per CU, margin 6
+        case 35: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 6, 0, rw_tune(kLeanFine, 1)); else break;
+        case 36: if constexpr (!GATHER) return RWT(768, 16, 16, -1, 5, 0, rw_tune(kLeanFine, 2)); else break;
+        case 37: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, rw_tune(kLeanFine, 2)); else break;
+        case 38: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, rw_tune(kLeanFine, 4)); else break;
+        case 39: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 6, 0, rw_tune(kRwOneFine, 2)); else break;
+        case 12: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 1, rw_tune(0, 4)); else break;      // the PRODUCT configuration (702), instrumented
+        case 13: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 2, rw_tune(0, 4)); else break;      // ... windows not staged (timing aid)
+        case 14: if constexpr (!GATHER) return RWT(512, 16, 16, -1, 4, 3, rw_tune(0, 4)); else break;      // ... LDS loop skipped (timing aid)
+        case 7: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 4, 1, rw_tune(0, 4)); else return RWT(512, 8, 16, 4, 5, 1, rw_tune(0, 4));
+        case 8: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 4, 2, rw_tune(0, 4)); else return RWT(512, 8, 16, 4, 5, 2, rw_tune(0, 4));
+        case 9: if constexpr (!GATHER) return RWT(256, 8, 16, -1, 4, 3, rw_tune(0, 4)); else return RWT(512, 8, 16, 4, 5, 3, rw_tune(0, 4));
         default: break;
         }
     }
     if constexpr (KL == 5 && !GATHER) {      // round 4: the product's shape for five levels (level 0 global, 16 x 16 regions)
-        if (cfg == 15) return RWT(512, 16, 16, -1, 4, 0, 20);
-        if (cfg == 18) return RWT(512, 16, 16, -1, 5, 0, 20);
-        if (cfg == 34) return RWT(768, 16, 16, -1, 4, 0, 310);      // lean registers, 12 waves per CU (margin 5 does not fit beside 96 octets' records)
-        if (cfg == 35) return RWT(640, 16, 16, -1, 5, 0, 310);      // 10 waves, margin 5
-        if (cfg == 36) return RWT(512, 16, 16, -1, 5, 0, 320);
-        if (cfg == 40) return RWT(768, 16, 16, -1, 4, 0, 1120);
-        if (cfg == 41) return RWT(1024, 16, 16, -1, 4, 0, 1110);
-        if (cfg == 48) return RWT(960, 24, 16, -1, 4, 0, 1110);      // 24 x 16 regions as for four levels: 15 waves is what fits beside the windows
-        if (cfg == 49) return RWT(896, 24, 16, -1, 4, 0, 1110);
+        if (cfg == 15) return RWT(512, 16, 16, -1, 4, 0, rw_tune(0, 2));
+        if (cfg == 18) return RWT(512, 16, 16, -1, 5, 0, rw_tune(0, 2));
+        if (cfg == 34) return RWT(768, 16, 16, -1, 4, 0, rw_tune(kLeanFine, 1));      // lean registers, 12 waves per CU (margin 5 does not fit beside 96 octets' records)
+        if (cfg == 35) return RWT(640, 16, 16, -1, 5, 0, rw_tune(kLeanFine, 1));      // 10 waves, margin 5
+        if (cfg == 36) return RWT(512, 16, 16, -1, 5, 0, rw_tune(kLeanFine, 2));
+        if (cfg == 40) return RWT(768, 16, 16, -1, 4, 0, rw_tune(kLeanFine | kRwRebuildTid, 2));
+        if (cfg == 41) return RWT(1024, 16, 16, -1, 4, 0, rw_tune(kLeanFine | kRwRebuildTid, 1));
+        if (cfg == 48) return RWT(960, 24, 16, -1, 4, 0, rw_tune(kLeanFine | kRwRebuildTid, 1));      // 24 x 16 regions as for four levels: 15 waves is what fits beside the windows
+        if (cfg == 49) return RWT(896, 24, 16, -1, 4, 0, rw_tune(kLeanFine | kRwRebuildTid, 1));
     }
-    if constexpr (KL == 4) return RWT(512, 8, 16, 4, 5, 0, 40);
-    else return RWT(512, 8, 16, 4, 4, 0, 40);      // five levels: the margin-5 windows do not fit 160 KB
+    if constexpr (KL == 4) return RWT(512, 8, 16, 4, 5, 0, rw_tune(0, 4));
+    else return RWT(512, 8, 16, 4, 4, 0, rw_tune(0, 4));      // five levels: the margin-5 windows do not fit 160 KB
 #undef RWT
 #undef RW
 }
@@ -197,10 +199,10 @@ int exp_launch_fast_forward(hipStream_t st, const float *value, const int64_t *s
         const size_t lds = (size_t)32 * (L * P + 1) * 32;
         // measured at the 800x1333 encoder shape, bs 4, with the head rotation of tile_of_block: 4x8 246 us, 8x4 252,
         // 2x16 253 (before the rotation: strips 299, 4x8 284, 8x4 281, 2x16 286)
-        if (g_fwd_variant == 408) LAUNCH_FWD(1, 4, 408, bound);
-        else if (g_fwd_variant == 216) LAUNCH_FWD(1, 4, 216, bound);
-        else if (g_fwd_variant == 804) LAUNCH_FWD(1, 4, 804, bound);
-        else LAUNCH_FWD(1, 4, 408, bound);
+        if (g_fwd_variant == 408) LAUNCH_FWD(1, 4, patch_hw(4, 8), bound);
+        else if (g_fwd_variant == 216) LAUNCH_FWD(1, 4, patch_hw(2, 16), bound);
+        else if (g_fwd_variant == 804) LAUNCH_FWD(1, 4, patch_hw(8, 4), bound);
+        else LAUNCH_FWD(1, 4, patch_hw(4, 8), bound);
         g_last_kernels = "msda_fwd_d32<1, 4, 408";
         return semidetr::launch_status("msda_fwd_d32<patch>");
     }
@@ -577,13 +579,13 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
             // measured at the encoder shape, bs 4: generic strips 370 us, unrolled strips 346 us; 66 / 67 force them
             const int gbound = (S + 31) / 32 * 5 / 4 + 4 * L;      // patch grid hint, see launch_fast_forward
             if (L * P == 16 && g_bwd_variant == 6962)            // tuning: 8 loads in flight, 6 waves per SIMD
-                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, 408, 6, 2>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
+                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8), 6, 2>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
                                    st, grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound);
             else if (L * P == 16 && g_bwd_variant == 6952)       // 8 loads in flight, 5 waves per SIMD
-                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, 408, 5, 2>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
+                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8), 5, 2>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
                                    st, grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound);
             else if (L * P == 16 && g_bwd_variant == 6948)       // timing aid: nothing stored
-                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, 408, 4, 104>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
+                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8), 4, 104>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
                                    st, grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound);
             else if (L * P == 16 && g_bwd_variant == 920) {       // four lanes per query, 8 x 8 patches (msda_bwd_gather4_d32)
                 const int gbound4 = (S + 63) / 64 * 5 / 4 + 4 * L;
@@ -592,19 +594,19 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
                                    grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound4,
                                    fill_in_gather ? reinterpret_cast<float4 *>(grad_value) : nullptr, (int64_t)(fill / 16));
             } else if (L * P == 16 && g_bwd_variant == 921)       // rolling window of 16 corner loads
-                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, 408, 4, 16>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
+                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8), 4, 16>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
                                    st, grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound,
                                    fill_in_gather ? reinterpret_cast<float4 *>(grad_value) : nullptr, (int64_t)(fill / 16));
             else if (L * P == 16 && g_bwd_variant == 922)         // rolling window of 8 corner loads, 5 waves per SIMD
-                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, 408, 5, 8>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
+                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8), 5, 8>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
                                    st, grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound,
                                    fill_in_gather ? reinterpret_cast<float4 *>(grad_value) : nullptr, (int64_t)(fill / 16));
             else if (fill_in_gather)
-                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, 408>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
+                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8)>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
                                    st, grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound,
                                    reinterpret_cast<float4 *>(grad_value), (int64_t)(fill / 16));
             else if (L * P == 16 && g_bwd_variant != 66 && g_bwd_variant != 67)
-                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, 408>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
+                hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8)>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
                                    st, grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound);
             else if (L * P == 16 && g_bwd_variant == 67)
                 hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16>), dim3((unsigned)((int64_t)N * gt * M)), dim3(256), glds, st,
@@ -665,7 +667,7 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
                     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
                     hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(512), rlds, st, grad_out, spatial_shapes, level_start, io, S, M, L, rbound, grad_value);
                 } else {
-                    auto kern = &msda_bwd_scatter_d32_reg<IO, 512, 176, 8, 16, 24, 32, 1, 6, 1004>;
+                    auto kern = &msda_bwd_scatter_d32_reg<IO, 512, 176, 8, 16, 24, 32, 1, 6, kWuPaired + 4>;
                     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
                     hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(512), rlds, st, grad_out, spatial_shapes, level_start, io, S, M, L, rbound, grad_value);
                 }
@@ -685,8 +687,8 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
                 hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(512), rlds, st, grad_out, spatial_shapes, level_start, io, S, M, L,
                                    rbound, grad_value);
             }
-            else if (g_bwd_variant == 6983) LAUNCH_REGU(512, 208, 8, 16, 24, 32, 4, 108);  // b128 entry reads, next batch prefetched
-            else if (g_bwd_variant == 6984) LAUNCH_REGU(512, 208, 8, 16, 24, 32, 4, 104);  // same, batches of 4
+            else if (g_bwd_variant == 6983) LAUNCH_REGU(512, 208, 8, 16, 24, 32, 4, kWuPipelined + 8);  // b128 entry reads, next batch prefetched
+            else if (g_bwd_variant == 6984) LAUNCH_REGU(512, 208, 8, 16, 24, 32, 4, kWuPipelined + 4);  // same, batches of 4
             else if (small) LAUNCH_REG(512, 208, 8, 16, 24, 32);
             else LAUNCH_REG(1024, 384, 16, 16, 32, 32);
 #undef LAUNCH_REG

@@ -672,6 +672,12 @@ __device__ __forceinline__ void fwd_stats_add(const FwdStats &fs, unsigned far, 
     }
 }
 
+// PATCH template arguments: patch_hw(PH, PW) = the workgroup's 32 queries are a PH x PW patch of one level; 0 = 32 consecutive queries.
+// (Packed in decimal, so that a kernel name reads "408" for 4 x 8.)
+constexpr int patch_hw(int h, int w) { return h * 100 + w; }
+constexpr int patch_h(int patch) { return patch / 100; }
+constexpr int patch_w(int patch) { return patch % 100; }
+
 // SPLIT = number of 8-lane groups that share one (q) row; each takes samples k = part, part+SPLIT, ...
 template <int SPLIT, int UNROLL, int PATCH = 0, typename IO = LocAttnIO>
 __global__ __launch_bounds__(256) void msda_fwd_d32(
@@ -687,7 +693,7 @@ __global__ __launch_bounds__(256) void msda_fwd_d32(
 
     Tile t = tile_of_block(M, tiles_per_image, RPB);
     const int rs = M * kD;
-    constexpr int PH = PATCH / 100, PW = PATCH % 100;
+    constexpr int PH = patch_h(PATCH), PW = patch_w(PATCH);
     static_assert(PATCH == 0 || (PH * PW == RPB && SPLIT == 1), "a patch holds exactly the workgroup's rows");
     Patch pt = {0, 0, 0, 0, 0};
     bool sampled = false;                 // this workgroup counts how far its samples reach (FwdStats)
@@ -1112,7 +1118,7 @@ __global__ __launch_bounds__(256) void msda_bwd_d32(
 // KLP = L * P at compile time (16: the DINO configuration) or 0.  With KLP the sample loop is fully unrolled, the
 // three sums of sample k stay in the registers of lane k % 8 of the group (no LDS store inside the loop, so the
 // compiler can keep 16 corner loads in flight like the forward does) and go to global memory straight from there.
-// PATCH = PH * 100 + PW: the 32 queries of a workgroup are a patch of one level (num_query == spatial_size), as in
+// PATCH = patch_hw(PH, PW): the 32 queries of a workgroup are a patch of one level (num_query == spatial_size), as in
 // the forward; 0: 32 consecutive queries.
 // The body is a device function of (virtual block, thread in 0..255, LDS base, active) so that the merged backward
 // launch (msda_bwd_lvl_merged) can run two of these per 512-thread workgroup next to its scatter workgroups; an
@@ -1139,7 +1145,7 @@ __device__ __forceinline__ void gather_body(
         lev_h[tid] = (float)shapes[2 * tid];
         lev_w[tid] = (float)shapes[2 * tid + 1];
     }
-    constexpr int PH = PATCH / 100, PW = PATCH % 100;
+    constexpr int PH = patch_h(PATCH), PW = patch_w(PATCH);
     static_assert(PATCH == 0 || PH * PW == RPB, "a patch holds exactly the workgroup's rows");
     Patch pt = {0, 0, 0, 0, 0};
     // level constants of this thread's sample slot, fetched once when L*P divides 256 (see msda_fwd_d32)

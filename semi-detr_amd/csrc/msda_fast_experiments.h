@@ -305,7 +305,7 @@ __global__ __launch_bounds__(kWinThreads, 4) void msda_bwd_enc_merged(
     const int half = (int)threadIdx.x >> 8;
     const int vb = 2 * gi + half;
     const size_t half_f4 = (size_t)2 * 32 * (L * P + 1) + 2 * kMaxLevels / 4 + 4;
-    gather_body<IO, KLP, 408, true>(vb, (int)threadIdx.x & 255, smem + half * half_f4, vb < gather_blocks, gout, value,
+    gather_body<IO, KLP, patch_hw(4, 8), true>(vb, (int)threadIdx.x & 255, smem + half * half_f4, vb < gather_blocks, gout, value,
                                     shapes, starts, io, S, M, L, S, P, gather_bound);
 }
 

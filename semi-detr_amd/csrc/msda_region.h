@@ -30,6 +30,15 @@ constexpr size_t reg_lds_bytes()
            (size_t)2 * WH * WW * 4 + (size_t)kRegQ * 4 + 8 * 4 + (NT / 64) * 4 + 4 * kMaxLevels * 4 + 64;
 }
 
+// WU = (mode of the row walk) + (entries per stream and trip, < 100); no mode: the plain walk
+constexpr int kWuPipelined = 100;      // shares start on even entries, two entries per ds_read_b128, the next batch requested ahead (see the walk)
+constexpr int kWuPaired = 1000;        // PAIRED corners: one entry per pair of horizontally neighbouring corners (see reg_scatter_body)
+template <int WU>
+struct ScatterWu {
+    static constexpr bool paired = WU >= kWuPaired, pipelined = WU >= kWuPipelined && WU < kWuPaired;
+    static constexpr int per_trip = WU % kWuPipelined;
+};
+
 // AID (experiments build only): timing aids, results wrong -- 1: no dot phase, 2: no row atomics, 4: no result stores,
 // 8: dot phase without its global loads, 16: dot phase without its LDS reads
 template <typename IO, int NT, int kRegQ, int RTH, int RTW, int WH, int WW, int DBG = 0, int WU = 8, int FUSE = 0, int AID = 0>
@@ -40,12 +49,12 @@ __device__ __forceinline__ void reg_scatter_body(
 {
     io.same_dims(S, M, L);
     constexpr int kWR = WH * WW, kNE = kRegQ * kPT * 4, SPT = (kRegQ * kPT + NT - 1) / NT, KC = (kWR + NT - 1) / NT;
-    // WU >= 1000: PAIRED corners.  The left and the right corner of a sample's top (bottom) edge land on NEIGHBOURING window rows, so
+    // kWuPaired: PAIRED corners.  The left and the right corner of a sample's top (bottom) edge land on NEIGHBOURING window rows, so
     // one 16-byte entry {w_left, w_right, word} bucketed by the LEFT row serves both: half the entries to count, fill and walk; the
     // walk keeps the sums of rows r and r + 1 and hands the second one on when the next run is row r + 1 (flag in the run's last entry),
     // so rows are flushed as often as before.  A corner whose partner is missing (level border) or outside the window goes to the miss
     // list on its own, as out-of-window corners always did.
-    constexpr bool kPair = WU >= 1000;
+    constexpr bool kPair = ScatterWu<WU>::paired;
     static_assert(!kPair || FUSE == 0, "the fused-backward experiment indexes one entry per corner");
     // round 5: the entry word of the plain walk carries the destination as a PIXEL OFFSET from the window's first pixel (15 bits:
     // (window row) * W + column) instead of the window row index the counting sort uses -- the flush then is one bit-field extract and
@@ -488,11 +497,11 @@ __device__ __forceinline__ void reg_scatter_body(
                                           (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)gimg_v);
                     (void)gimg;
                     const int total = (AID & 64) ? 0 : stats[3];      // aid 64: no walk at all
-                    // WU >= 100: shares start on even entries (16-byte aligned: two entries per ds_read_b128, which moves twice
+                    // kWuPipelined: shares start on even entries (16-byte aligned: two entries per ds_read_b128, which moves twice
                     // the bytes per LDS cycle of the ds_read2_b64 the compiler picks for single entries) and the entries of batch
                     // i + 1 are requested before batch i is processed
-                    constexpr bool kPipe = WU >= 100 && WU < 1000;
-                    constexpr int WB = WU % 100;
+                    constexpr bool kPipe = ScatterWu<WU>::pipelined;
+                    constexpr int WB = ScatterWu<WU>::per_trip;
                     const int lo = kPipe ? ((int)((int64_t)total * sid / kStreams) & ~1) : (int)((int64_t)total * sid / kStreams);
                     const int hi = kPipe ? (sid + 1 == kStreams ? total : ((int)((int64_t)total * (sid + 1) / kStreams) & ~1))
                                          : (int)((int64_t)total * (sid + 1) / kStreams);
@@ -569,7 +578,7 @@ __device__ __forceinline__ void reg_scatter_body(
                                 open_r = false;
                             }
                         };
-                        constexpr int WB = WU % 100;
+                        constexpr int WB = ScatterWu<WU>::per_trip;
                         for (; e + WB <= hi; e += WB) {
                             float4 en[WB];
                             float2 gq[WB];
@@ -633,23 +642,23 @@ __device__ __forceinline__ void reg_scatter_body(
                                 if (e + u < hi) step(en[u], gq[u]);
                         }
                     } else {
-                    for (; e + WU <= hi; e += WU) {
-                        float2 en[WU], gq[WU];
+                    for (; e + WB <= hi; e += WB) {
+                        float2 en[WB], gq[WB];
 #pragma unroll
-                        for (int u = 0; u < WU; ++u) en[u] = entries[e + u];
+                        for (int u = 0; u < WB; ++u) en[u] = entries[e + u];
 #pragma unroll
-                        for (int u = 0; u < WU; ++u) gq[u] = gq_of(en[u].y);
+                        for (int u = 0; u < WB; ++u) gq[u] = gq_of(en[u].y);
 #pragma unroll
-                        for (int u = 0; u < WU; ++u) step(en[u], gq[u]);
+                        for (int u = 0; u < WB; ++u) step(en[u], gq[u]);
                     }
-                    if (e < hi) {       // tail of < WU entries
-                        float2 en[WU], gq[WU];
+                    if (e < hi) {       // tail of < WB entries
+                        float2 en[WB], gq[WB];
 #pragma unroll
-                        for (int u = 0; u < WU; ++u) en[u] = entries[min(e + u, hi - 1)];
+                        for (int u = 0; u < WB; ++u) en[u] = entries[min(e + u, hi - 1)];
 #pragma unroll
-                        for (int u = 0; u < WU; ++u) gq[u] = gq_of(en[u].y);
+                        for (int u = 0; u < WB; ++u) gq[u] = gq_of(en[u].y);
 #pragma unroll
-                        for (int u = 0; u < WU; ++u)
+                        for (int u = 0; u < WB; ++u)
                             if (e + u < hi) step(en[u], gq[u]);
                     }
                     }
@@ -746,7 +755,7 @@ __global__ __launch_bounds__(512, 6) void msda_bwd_scatter_d32_reg_pair_aid(
 {
     io.same_dims(S, M, L);
     extern __shared__ float4 smem[];
-    reg_scatter_body<IO, 512, 176, 8, 16, 24, 32, 0, 1004, 0, AID>((int)blockIdx.x, smem, gout, shapes, starts, io, S, M, L, regions_bound, gvalue);
+    reg_scatter_body<IO, 512, 176, 8, 16, 24, 32, 0, kWuPaired + 4, 0, AID>((int)blockIdx.x, smem, gout, shapes, starts, io, S, M, L, regions_bound, gvalue);
 }
 // timing aid (backward variant 6985, results wrong): the region scatter WITHOUT its row atomics -- what the compute side alone costs
 template <typename IO>
@@ -805,7 +814,7 @@ __global__ __launch_bounds__(512, 4) void msda_bwd_encreg_merged(
     const int half = (int)threadIdx.x >> 8;
     const int vb = 2 * gi + half;
     const size_t half_f4 = (size_t)2 * 32 * (L * P + 1) + 2 * kMaxLevels / 4 + 4;
-    gather_body<IO, KLP, 408, true>(vb, (int)threadIdx.x & 255, smem + half * half_f4, vb < gather_blocks, gout, value,
+    gather_body<IO, KLP, patch_hw(4, 8), true>(vb, (int)threadIdx.x & 255, smem + half * half_f4, vb < gather_blocks, gout, value,
                                     shapes, starts, io, S, M, L, S, P, gather_bound);
 }
 #endif

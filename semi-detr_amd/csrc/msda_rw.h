@@ -4,9 +4,10 @@
 // msda_fast.h / msda_region.h.  PRODUCT since round 4: the forward instantiations <768 threads, regions of up to 25 x 16 pixels, level 0
 // through global loads, margin 5 on the coarse levels> for four levels and <960 threads, up to 24 x 16, margin 4> for five are what
 // launch_fast_forward picks while most samples stay within a few pixels of their queries (FwdStats); the other
-// configurations and the gather half are reachable from the experiments library only.  The TUNE flags (scheduling barriers, level-0
-// samples in flight, which values are rebuilt per round / region instead of held in registers) are listed at msda.hip's
-// SEMIDETR_RW_TUNE; tools/rw_regs.sh compiles one configuration in seconds and prints its VGPRs and spills.
+// configurations and the gather half are reachable from the experiments library only.  A configuration is the template argument TUNE =
+// rw_tune(named flags, samples between scheduling barriers, pre-issued out-of-window samples), defined and decoded below (kRw..., RwTune)
+// and nowhere else; the product's are msda.hip's SEMIDETR_RW_TUNE...; tools/rw_regs.sh compiles one configuration in seconds and prints
+// its VGPRs and spills.
 //
 // Why.  The patch kernels (msda_fwd_d32<1,4,408>, msda_bwd_gather_d32) pull every corner row through the vector-memory
 // path: 4 x 22223 x 8 heads x 16 samples x 4 corners x 128 B = 5.8 GB per bs-4 launch at 64 B/clk/CU -- TA busy 80 %,
@@ -53,6 +54,51 @@
 #endif
 constexpr int kRwHeadRun = 16;      // head rotation of the region kernels (see tile_of_block)
 
+// ---- TUNE: the configuration of msda_rw_d32 as ONE template argument.  Flags (every combination gives the same results) ...
+enum : int {
+    kRwOneFine = 1,          // one level-0 sample's corner loads in flight instead of two (-33 VGPRs)
+    kRwLean = 2,             // "lean": the per-lane level constants are re-selected where they are used, the staging coordinates rebuilt per region
+    kRwOneOowPerTrip = 4,    // one instead of two out-of-window samples per trip of the fall-back loop
+    kRwRebuildTid = 8,       // everything else derived from the thread index (octet / window addresses, per-level lane values, division
+                             // reciprocals of the region grid) rebuilt per round / region through an empty asm: what fits 1024 threads into 128 VGPRs
+    kRwSplitLoad = 16,       // the prefetched sampling data stay as loaded; the fused prologue's location arithmetic runs in the consuming round
+    kRwMadU16 = 32,          // window addresses by v_mad_u32_u16, packed FMAs with explicit op_sel (measured level; experiments)
+    kRwLevelTable = 64,      // (round 5, with kRwLean and kRwSplitLoad) the per-lane level constants of the geometry come from a 48-byte-per-level
+                             // table in LDS, three ds_read_b128 per pass, instead of one v_mov + v_cndmask pair per constant (gfx950 VALU
+                             // instructions take ONE scalar operand, so "select between two wave-uniform values" is two instructions: 100 of the
+                             // ~300 the geometry of a round took)
+    kRwQueryList = 128,      // the region's query list (slot -> query) is worked out once per region into LDS; a round reads its slot instead of
+                             // redoing the level search, five shuffles and a division (~35 instructions and 7 ds_bpermute per round)
+    kRwCompact = 256,        // (with kRwLevelTable; forward) COMPACT records for out-of-window samples: where the geometry finds a sample outside
+                             // its window it writes {lw, lh, attention, top-left pixel} into the sample's own weight record (its rows are the zero
+                             // rows, so the LDS loop adds 0 x finite), and the out-of-window loop builds the four corner offsets from that and the
+                             // level table on all eight lanes -- instead of the owner lane redoing the whole geometry from (x, y) inside a branch
+                             // (publish), a slot write, a wait and a slot read per sample.  The sampling data (x, y, attention of both passes) die
+                             // before the LDS loop.
+    kRwWideOffsets = 512,    // (forward, level 0 through global loads) a sample's two window offsets as two 32-bit byte offsets: 8 instead of 4
+                             // bytes per record, 2 instead of 5 VALU instructions per sample of the LDS loop, no packing in the geometry
+    kRwTailSplit = 1024,     // the tail split of small launches (helper workgroups take part of the rounds of the last wave's units, see the kernel)
+};
+// ... packed in decimal with two counts, so that a configuration reads off the kernel names of a profile (DESIGN.md 2.3b has the table
+// flag -> historical addend): 100 * flags + 10 * (compute-loop samples between scheduling barriers) + (out-of-window samples per octet whose
+// loads are issued ahead of the compute loop: with level 0 through global loads their slots need 64 more bytes per octet; measured level, 0 in
+// the product).  These two definitions are the only places that know the packing.
+// Round 4's product: rw_tune(kRwSplitLoad | kRwLean | kRwOneFine, 2) = 1920 (four levels), rw_tune(kRwRebuildTid | kRwLean | kRwOneFine, 1) = 1110 (five).
+constexpr int rw_tune(int flags, int samples_per_barrier, int preissued = 0) { return 100 * flags + 10 * samples_per_barrier + preissued; }
+struct RwTuneFields { int flags, samples_per_barrier, preissued; };
+constexpr RwTuneFields rw_untune(int tune) { return RwTuneFields{tune / 100, (tune / 10) % 10, tune % 10}; }
+// (a configuration given as a plain integer -- a tuning build's -D, an archived A/B record -- with flags added / another barrier spacing)
+constexpr int rw_tune_or(int tune, int flags) { return rw_tune(rw_untune(tune).flags | flags, rw_untune(tune).samples_per_barrier, rw_untune(tune).preissued); }
+constexpr int rw_tune_spaced(int tune, int samples_per_barrier) { return rw_tune(rw_untune(tune).flags, samples_per_barrier, rw_untune(tune).preissued); }
+template <int TUNE>
+struct RwTune {
+    static constexpr int flags = rw_untune(TUNE).flags, samples_per_barrier = rw_untune(TUNE).samples_per_barrier, preissued = rw_untune(TUNE).preissued;
+    static constexpr bool one_fine = (flags & kRwOneFine) != 0, lean = (flags & kRwLean) != 0, one_oow_per_trip = (flags & kRwOneOowPerTrip) != 0;
+    static constexpr bool rebuild_tid = (flags & kRwRebuildTid) != 0, split_load = (flags & kRwSplitLoad) != 0, mad_u16 = (flags & kRwMadU16) != 0;
+    static constexpr bool level_table = (flags & kRwLevelTable) != 0, query_list = (flags & kRwQueryList) != 0, compact = (flags & kRwCompact) != 0;
+    static constexpr bool wide = (flags & kRwWideOffsets) != 0, tail = (flags & kRwTailSplit) != 0;
+};
+
 // Window geometry at compile time.  Level l of a halving pyramid sees the region as (RTH >> l) x (RTW >> l) pixels;
 // H0 / HC = margin in pixels around it on level 0 / on the coarser levels (whose pixel centres are not aligned with
 // the region's edges: one more row / column).  Widths are rounded up to odd (bank parity, see above).
@@ -83,7 +129,7 @@ struct RwWin {
 template <int KL, bool FG = false, bool PRE = false, bool WIDE = false>
 constexpr int rw_oct_bytes()      // per octet: {float4 record} and {two 16-bit window offsets} per windowed sample | two 32-byte slots (+ bank spread)
 {
-    // WIDE (TUNE + 51200, forward with level 0 through global loads): the two window offsets of a sample as two 32-bit BYTE offsets --
+    // WIDE (kRwWideOffsets, forward with level 0 through global loads): the two window offsets of a sample as two 32-bit BYTE offsets --
     // the loop adds the lane's base to each (2 VALU per sample instead of shift / mask / add / bit-field extract / shift-add)
     if (WIDE) {
         constexpr int raww = (KL - 1) * kPT * 24 + kPT * 32;
@@ -91,7 +137,7 @@ constexpr int rw_oct_bytes()      // per octet: {float4 record} and {two 16-bit 
     }
     // level 0 without a window (FG): its samples have no window record; their {corner offsets, weights} records (32 bytes each) are
     // dead by the time the out-of-window loop needs its two slots, so the slots lie on top of them -- unless out-of-window samples
-    // are pre-issued (PRE: TUNE % 10 > 0), whose slots are written while those records are still live
+    // are pre-issued (PRE: RwTune::preissued > 0), whose slots are written while those records are still live
     constexpr int raw = FG ? (KL - 1) * kPT * 20 + kPT * 32 + (PRE ? 64 : 0) : KL * kPT * 20 + 64;
     return raw + (raw % 128 == 0 ? 16 : 0);      // octet pitch: A, B, C, D on distinct banks
 }
@@ -102,12 +148,13 @@ constexpr int rw_oct_bytes()      // per octet: {float4 record} and {two 16-bit 
 // compares per row / corner; a level without one (vh < 0) reads the mask's bytes: beside the staging loads for the windows (no
 // dependent load), from global memory for level-0 corners and out-of-window samples (correct for any mask; only the summarised
 // form is fast).
-constexpr int kRwQList = 1024;      // TUNE + 12800: slots of the region's query list in LDS (regions with more queries work them out per round)
+constexpr int kRwQList = 1024;      // kRwQueryList: slots of the region's query list in LDS (regions with more queries work them out per round)
 template <int NT, int RTH, int RTW, int H0, int HC, int KL, int TUNE = 0>
 constexpr size_t rw_lds_bytes()
 {
-    return (size_t)RwWin<RTH, RTW, H0, HC, KL>::total * 128 + (size_t)(NT / 8) * rw_oct_bytes<KL, (H0 < 0), (TUNE % 10 > 0), (((TUNE / 100) & 512) != 0)>() +
-           (((TUNE / 100) & 64) ? (size_t)(KL + 1) * 48 : 0) + (((TUNE / 100) & 128) ? (size_t)kRwQList * 4 : 0);
+    using T = RwTune<TUNE>;
+    return (size_t)RwWin<RTH, RTW, H0, HC, KL>::total * 128 + (size_t)(NT / 8) * rw_oct_bytes<KL, (H0 < 0), (T::preissued > 0), T::wide>() +
+           (T::level_table ? (size_t)(KL + 1) * 48 : 0) + (T::query_list ? (size_t)kRwQList * 4 : 0);
 }
 
 // smallest q in [0, nq] with ((2 q + 1) * nb) / (2 * nq) >= bound  (the first pixel of a level with nq rows whose centre
@@ -157,31 +204,8 @@ __device__ __forceinline__ void rw_fma4(float4 &acc, const float4 &w, const floa
 // DBG (tuning builds only): 1 = per-phase cycle counts of wave 0 into g_dest_dbg, 2 = windows not staged (results
 // wrong, timing aid), 3 = compute loop skipped (results wrong, timing aid), 4 = out-of-window samples dropped, 5 = level-0 samples
 // (global loads) dropped, 7 = 3 + 5, 8 = 3 + 4 + 5 (what is left: staging, sampling-data loads, geometry, records, result stores)
-// TUNE = 100 * flags + 10 * (compute-loop samples between scheduling barriers) + (out-of-window samples per octet whose loads are
-//        issued ahead of the compute loop: with level 0 through global loads their slots need 64 more bytes per octet; measured level,
-//        0 in the product).  Flags (every combination gives the same results):
-//          1  one level-0 sample's corner loads in flight instead of two (-33 VGPRs)
-//          2  "lean": the per-lane level constants are re-selected where they are used, the staging coordinates rebuilt per region
-//          4  one instead of two out-of-window samples per trip of the fall-back loop
-//          8  everything else derived from the thread index (octet / window addresses, per-level lane values, division
-//             reciprocals of the region grid) rebuilt per round / region through an empty asm: what fits 1024 threads into 128 VGPRs
-//         16  the prefetched sampling data stay as loaded; the fused prologue's location arithmetic runs in the consuming round
-//         32  window addresses by v_mad_u32_u16, packed FMAs with explicit op_sel (measured level; experiments)
-//         64  (round 5, with 2 and 16) the per-lane level constants of the geometry come from a 48-byte-per-level table in LDS, three
-//             ds_read_b128 per pass, instead of one v_mov + v_cndmask pair per constant (gfx950 VALU instructions take ONE scalar
-//             operand, so "select between two wave-uniform values" is two instructions: 100 of the ~300 the geometry of a round took)
-//        256  (with 64; forward) COMPACT records for out-of-window samples: where the geometry finds a sample outside its window it
-//             writes {lw, lh, attention, top-left pixel} into the sample's own weight record (its rows are the zero rows, so the LDS
-//             loop adds 0 x finite), and the out-of-window loop builds the four corner offsets from that and the level table on all
-//             eight lanes -- instead of the owner lane redoing the whole geometry from (x, y) inside a branch (publish), a slot write,
-//             a wait and a slot read per sample.  The sampling data (x, y, attention of both passes) die before the LDS loop.
-//        512  (forward, level 0 through global loads) a sample's two window offsets as two 32-bit byte offsets: 8 instead of 4 bytes
-//             per record, 2 instead of 5 VALU instructions per sample of the LDS loop, no packing in the geometry
-//       1024  the tail split of small launches (helper workgroups take part of the rounds of the last wave's units, see the kernel)
-//        128  the region's query list (slot -> query) is worked out once per region into LDS; a round reads its slot instead of
-//             redoing the level search, five shuffles and a division (~35 instructions and 7 ds_bpermute per round)
-//        Product: 1920 = 16 + 2 + 1, two samples per barrier (four levels); 1110 = 8 + 2 + 1, one sample per barrier (five levels).
-template <typename IO, int NT, int RTH, int RTW, int H0, int HC, int KL, bool GATHER, int DBG = 0, int TUNE = 42, bool MASK = false>
+// TUNE: the configuration, rw_tune(flags, samples between scheduling barriers, pre-issued out-of-window samples) -- see RwTune above.
+template <typename IO, int NT, int RTH, int RTW, int H0, int HC, int KL, bool GATHER, int DBG = 0, int TUNE = rw_tune(0, 4, 2), bool MASK = false>
 __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(      // 256-thread workgroups: two per CU
     const float *__restrict__ gout, const float *__restrict__ value, const int64_t *__restrict__ shapes,
     const int64_t *__restrict__ starts, const IO io, int S, int M, int regions_bound, float *__restrict__ out,
@@ -191,11 +215,12 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
     using Wn = RwWin<RTH, RTW, H0, HC, KL>;
     constexpr int P = kPT, KLP = KL * P, G = NT / 8, NPASS = (KLP + 7) / 8;
     constexpr bool FG = Wn::fine_global;                  // level 0 through global loads (forward only)
-    constexpr bool kWide = ((TUNE / 100) & 512) != 0;
-    static_assert(!kWide || (FG && !GATHER && TUNE % 10 == 0), "wide window offsets: the forward's product shape");
-    constexpr int kOctBytes = rw_oct_bytes<KL, FG, (TUNE % 10 > 0), kWide>();
+    using T = RwTune<TUNE>;
+    constexpr bool kWide = T::wide;
+    static_assert(!kWide || (FG && !GATHER && T::preissued == 0), "wide window offsets: the forward's product shape");
+    constexpr int kOctBytes = rw_oct_bytes<KL, FG, (T::preissued > 0), kWide>();
     constexpr int kRec0 = FG ? P : 0;                     // first sample with a window record
-    constexpr int kOffAt = (KLP - kRec0) * 16, kFineAt = (KLP - kRec0) * (kWide ? 24 : 20), kSlotAt = (FG && TUNE % 10 > 0) ? kFineAt + P * 32 : kFineAt;
+    constexpr int kOffAt = (KLP - kRec0) * 16, kFineAt = (KLP - kRec0) * (kWide ? 24 : 20), kSlotAt = (FG && T::preissued > 0) ? kFineAt + P * 32 : kFineAt;
     static_assert(Wn::total * 128 <= (1 << 20), "window offsets are kept in 16 bits, in units of 16 bytes");
     constexpr unsigned kZ0 = (unsigned)Wn::zrow * 128u;
     static_assert(P == 4 && KLP <= 32, "lane j of an octet owns samples j, j + 8, ...");
@@ -205,13 +230,13 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
     extern __shared__ float4 smem[];
     char *const lds = reinterpret_cast<char *>(smem);
     char *const recs = lds + Wn::total * 128;
-    constexpr bool kTab = ((TUNE / 100) & 64) != 0, kQList = ((TUNE / 100) & 128) != 0, kCompact = ((TUNE / 100) & 256) != 0;
-    static_assert(!kCompact || (kTab && !GATHER && TUNE % 10 == 0), "compact out-of-window records: forward, level table, nothing pre-issued");
+    constexpr bool kTab = T::level_table, kQList = T::query_list, kCompact = T::compact;
+    static_assert(!kCompact || (kTab && !GATHER && T::preissued == 0), "compact out-of-window records: forward, level table, nothing pre-issued");
     // (round 6, SEMIDETR_BRFREE) the window loop -- with the level-0 corner loads issued inside it -- is not wrapped in the "plain round"
     // branch: a plain round (rare: more than a third of the samples outside their windows) points every record at the zero rows and runs it
     // for nothing, the common round has one basic block less around loads in flight
     constexpr bool kLoopAlways = SEMIDETR_BRFREE && kCompact;
-    static_assert(!kTab || (((TUNE / 100) & 2) && ((TUNE / 100) & 16) && !GATHER && H0 < 0), "the level table serves the lean forward with split loads");
+    static_assert(!kTab || (T::lean && T::split_load && !GATHER && H0 < 0), "the level table serves the lean forward with split loads");
     // level table: per level {H, W, start, window row0 | window rows - 1, window columns - 1, window pitch, window origin y |
     //                          window origin x, (float)H, (float)W, -}; then the query list
     int4 *const ltab = reinterpret_cast<int4 *>(recs + (NT / 8) * kOctBytes);
@@ -268,9 +293,9 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
     // `tail_cus` helper workgroups appended to the grid (dispatched last; the ones not needed leave at once).  Each part stages the
     // region's windows again (8 % of a unit), so the last wave takes ~0.6 instead of 1 unit time.  tail_cus = 0: no helpers.
     // Small launches only, see s_ below.
-    // It is its own instantiation (TUNE + 102400), launched for small launches only: with the code merely PRESENT the four-image launch
+    // It is its own instantiation (kRwTailSplit), launched for small launches only: with the code merely PRESENT the four-image launch
     // measured 1.7 % slower inside the step (different schedule of the same loop), which is more than the one-image launch gains.
-    constexpr bool kTail = !GATHER && ((TUNE / 100) & 1024) != 0;
+    constexpr bool kTail = !GATHER && T::tail;
     int b_unit = b, part = 0, nparts = 1;
     if (kTail && tail_cus > 0) {
         const int nreg_all = nry * nrx, base_grid = (int)gridDim.x - tail_cus;
@@ -350,10 +375,10 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
         my_row0[p] = __shfl(r_row0, l, 64);
     }
 
-    // TUNE >= 200: no per-lane copies of the level constants (22 VGPRs that live through the whole kernel); a pass's two levels
+    // kRwLean: no per-lane copies of the level constants (22 VGPRs that live through the whole kernel); a pass's two levels
     // are compile-time, so each constant is ONE select between two wave-uniform values, redone where it is needed (the lane
     // predicate goes through an empty asm so that the selects are not hoisted back out of the round loop)
-    constexpr bool kLean = ((TUNE / 100) & 2) != 0;
+    constexpr bool kLean = T::lean;
     static_assert(!kLean || P == 4, "a pass covers two levels: lanes 0-3 / 4-7");
     struct LvlC { int l, H, W, st, wh1, ww1, ww, row0; };
     auto lvlc = [&](int p) -> LvlC {
@@ -384,8 +409,8 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
     auto run_regions = [&](auto bytes_tag) {
     constexpr bool kBytes = MASK && decltype(bytes_tag)::value;
     for (int reg = slot0; reg < nregions; reg += regions_bound) {
-        int Hb_r = Hb_k, Wb_r = Wb_k, nrx_r = nrx_k;      // TUNE + 800: ... and the reciprocals of the divisions by these
-        if ((TUNE / 100) & 8) asm volatile("" : "+s"(Hb_r), "+s"(Wb_r), "+s"(nrx_r));
+        int Hb_r = Hb_k, Wb_r = Wb_k, nrx_r = nrx_k;      // kRwRebuildTid: ... and the reciprocals of the divisions by these
+        if (T::rebuild_tid) asm volatile("" : "+s"(Hb_r), "+s"(Wb_r), "+s"(nrx_r));
         const int Hb = Hb_r, Wb = Wb_r, nrx = nrx_r;
         // BALANCED tiling: the grid's ceil(H / RTH) x ceil(W / RTW) regions share the rows / columns evenly (heights differ by at most
         // one row, none exceeds RTH: what the windows are sized for) instead of leaving a sliver at the bottom and right edges -- a
@@ -393,13 +418,13 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
         const int nry_b = (Hb + RTH - 1) / RTH, ry_b = reg / nrx, rx_b = reg - ry_b * nrx;
         const int y0b = (ry_b * Hb) / nry_b, y1b = ((ry_b + 1) * Hb) / nry_b;
         const int x0b = (rx_b * Wb) / nrx, x1b = ((rx_b + 1) * Wb) / nrx;
-        // TUNE + 800: the per-level lane values are rebuilt per region from their wave-uniform copies (one select per level)
+        // kRwRebuildTid: the per-level lane values are rebuilt per region from their wave-uniform copies (one select per level)
         // instead of living in six registers from the kernel's first instruction on
         int lane_t = tid;
-        if ((TUNE / 100) & 8) asm volatile("" : "+v"(lane_t));
+        if (T::rebuild_tid) asm volatile("" : "+v"(lane_t));
         const int lane_g = lane_t & 63;
         int g_H = r_H_k, g_W = r_W_k, g_st = r_st_k, g_wh = r_wh_k, g_ww = r_ww_k, g_row0 = r_row0_k;
-        if ((TUNE / 100) & 8) {
+        if (T::rebuild_tid) {
             g_H = g_W = g_wh = g_ww = 1;
             g_st = g_row0 = 0;
 #pragma unroll
@@ -473,9 +498,9 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
             return ok ? st_ + (yl + dy) * W_ + xl + (s - dy * w_) : -1;
         };
         // raw sample data of a round: loaded one round ahead of its use
-        // (TUNE + 1600: the loads' results stay as they arrive and the location arithmetic of the fused prologue runs at the START of
+        // (kRwSplitLoad: the loads' results stay as they arrive and the location arithmetic of the fused prologue runs at the START of
         //  the round that uses them -- done where the loads are issued it waits for them a round early)
-        constexpr bool kSplitLoad = ((TUNE / 100) & 16) != 0;
+        constexpr bool kSplitLoad = T::split_load;
         typename IO::RawXY rr[NPASS];
         float rx[NPASS], ry[NPASS], ra[NPASS];
         float4 go = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -602,10 +627,10 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
             // loop (no workgroup barrier inside) instead of spending issue slots on empty octets -- a region's 340 queries fill
             // 3.5 rounds of 96
             if (!__any(q >= 0)) break;
-            // TUNE + 800: the thread index goes through an empty asm once per round, so that what is derived from it (octet and
+            // kRwRebuildTid: the thread index goes through an empty asm once per round, so that what is derived from it (octet and
             // window addresses, the lane's byte offset) is rebuilt here instead of living in registers through the whole kernel
             int tid_r = tid;
-            if ((TUNE / 100) & 8) asm volatile("" : "+v"(tid_r));
+            if (T::rebuild_tid) asm volatile("" : "+v"(tid_r));
             const int oc = tid_r >> 3, j8 = tid_r & 7, cls = (tid_r >> 4) & 1, lane = tid_r & 63;
             const unsigned lane_b = (unsigned)(m * kD + 4 * j8) * 4u;
             char *const orec = recs + oc * kOctBytes;
@@ -904,7 +929,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
             };
             // ---- the first two out-of-window samples of every octet: corner loads issued NOW, consumed after the LDS loop
             //      (their latency hides behind it); further ones take the loop at the end
-            constexpr int kPre = TUNE % 10, kSB = (TUNE / 10) % 10;
+            constexpr int kPre = T::preissued, kSB = T::samples_per_barrier;
             bool pact[kPre > 0 ? kPre : 1];
             int pk[kPre > 0 ? kPre : 1];
             float4 pg[kPre > 0 ? kPre : 1], pv[kPre > 0 ? kPre : 1][4];
@@ -932,7 +957,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
             }
             // ---- level 0 without a window: its 4 x 4 corner rows come through the vector-memory path, issued now and
             //      consumed after the LDS loop (the two pipes work side by side)
-            constexpr int kFineN = (TUNE / 100) & 1 ? 1 : 2;      // level-0 samples in flight at a time (registers: 20 each)
+            constexpr int kFineN = T::one_fine ? 1 : 2;      // level-0 samples in flight at a time (registers: 20 each)
             constexpr int kFineGroups = P / kFineN, kFineStep = (KLP - P) / kFineGroups > 0 ? (KLP - P) / kFineGroups : 1;
             float4 fv[FG ? kFineN : 1][4], fw[FG ? kFineN : 1];
             int fine_cur = 0;                               // first level-0 sample of the group in flight
@@ -955,7 +980,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
                         RW_GATHER_STEP(0, fine_cur + i, fv[i][0], fv[i][1], fv[i][2], fv[i][3], fw[i].x, fw[i].y, fw[i].z);
                         continue;
                     }
-                    if constexpr (((TUNE / 100) & 32) != 0) {
+                    if constexpr (T::mad_u16) {
                         rw_fma4(acc, fw[i], fv[i][0], fv[i][1], fv[i][2], fv[i][3]);
                         continue;
                     }
@@ -981,8 +1006,8 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
                         const uint2 ow = *reinterpret_cast<const uint2 *>(orec + kOffAt + (k - kRec0) * 8);
                         a0 = wbase + ow.x;
                         a1 = wbase + ow.y;
-                    } else if constexpr (((TUNE / 100) & 32) != 0) {
-                        // TUNE + 3200: window address = base + 16 x (16-bit offset) as ONE v_mad_u32_u16 each (op_sel picks the half of
+                    } else if constexpr (T::mad_u16) {
+                        // kRwMadU16: window address = base + 16 x (16-bit offset) as ONE v_mad_u32_u16 each (op_sel picks the half of
                         // the packed word) instead of shift / mask / add: 2 instead of 5 VALU instructions per sample
                         unsigned u0, u1;
                         typedef const __attribute__((address_space(3))) char *lds_cptr;      // 32-bit LDS addresses, no base to add
@@ -1000,7 +1025,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
                     const float4 f3 = *reinterpret_cast<const float4 *>(a0 + pitch);
                     const float4 f4 = *reinterpret_cast<const float4 *>(a1 + pitch);
                     if (!GATHER) {
-                        if constexpr (((TUNE / 100) & 32) != 0) {
+                        if constexpr (T::mad_u16) {
                             rw_fma4(acc, r, f1, f2, f3, f4);
                         } else {
                             acc.x = fmaf(r.w, f4.x, fmaf(r.z, f3.x, fmaf(r.y, f2.x, fmaf(r.x, f1.x, acc.x))));
@@ -1055,7 +1080,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
             while (__any(gmask != 0)) {
                 // kTrip such samples per octet and trip (one slot each): 4 * kTrip corner loads in flight per lane, as in the
                 // plain kernels -- a trip costs one global round trip whatever it carries
-                constexpr int kTrip = ((TUNE / 100) & 4) ? 1 : 2;      // <= the octet's slots (four per trip measured no better: 222 vs 216 us; TUNE + 400: one, 20 VGPRs less)
+                constexpr int kTrip = T::one_oow_per_trip ? 1 : 2;      // <= the octet's slots (four per trip measured no better: 222 vs 216 us; kRwOneOowPerTrip: one, 20 VGPRs less)
                 bool act2[kTrip];
                 int k2[kTrip];
                 if constexpr (kCompact) {

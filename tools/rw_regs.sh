@@ -1,6 +1,7 @@
 #!/bin/bash
 # quick register / spill check of ONE region-window configuration (seconds instead of the whole library):
-#   tools/rw_regs.sh "LocAttnIO, 768, 16, 16, -1, 6, 4, false, 0, 20" [kernel name, default msda_rw_d32]
+#   tools/rw_regs.sh "LocAttnIO, 768, 16, 16, -1, 6, 4, false, 0, rw_tune(kRwLean | kRwOneFine, 2)" [kernel name, default msda_rw_d32]
+# (the last argument is msda_rw.h's TUNE: a named expression or, from an old record, its integer -- 320 for the one above)
 cd /root/repo
 mkdir -p /tmp/asm
 K=${2:-msda_rw_d32}
