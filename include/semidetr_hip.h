@@ -198,6 +198,38 @@ int semidetr_msda_gather_choice(int slot);
 const char *semidetr_msda_last_kernels(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * MSDA on fp16 / bf16 value maps (ABI 7, additive): what torch.autocast hands MSDeformAttn
+ * (detr_od/models/utils/ops/modules/ms_deform_attn.py:113-120, the "for amp" branch) without the fp32 copies of that branch.
+ *
+ * value, out, grad_out and grad_value hold `dtype` elements (SEMIDETR_H16_FP16: IEEE binary16, SEMIDETR_H16_BF16: bfloat16),
+ * 2-byte aligned; sampling_loc, attn_weight and their gradients are fp32 as above; layouts as above.
+ * Contract: every result is the fp32 op applied to the EXACTLY up-cast value / grad_out; out and grad_value are then rounded
+ * ONCE, to nearest even, into `dtype` (fp16 overflows to inf as the conversion does); grad_sampling_loc / grad_attn_weight are
+ * returned in fp32, unrounded.  Nothing is accumulated in 16 bits, locations and weights are never narrowed, the pixel mapping
+ * rounds exactly as in the fp32 op, corners outside a level are never loaded.  forward writes every element of `out`.
+ * backward: `workspace` = semidetr_msda_backward_h16_workspace_bytes(batch, spatial_size, num_heads, channels) bytes of device
+ *   memory (batch * spatial_size * num_heads * channels floats, 4-byte aligned; 16-byte aligned for the fastest conversion) that
+ *   the CALLER has zero-filled on `stream`: grad_value is accumulated there with fp32 atomics and converted by a last kernel,
+ *   which writes every element of grad_value.
+ * channels == 32, num_heads <= 32, 8-byte aligned value / out / grad_out: the fast kernels (any query set); everything else the
+ *   reference accepts under AMP (any channels, any head count, value on any 2-byte boundary): one wavefront per (n, q, m) row.
+ * semidetr_msda_h16_last_kernels: as semidetr_msda_last_kernels, for the last semidetr_msda_*_h16 call of the calling thread.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_H16_FP16 0
+#define SEMIDETR_H16_BF16 1
+int semidetr_msda_forward_h16(void *stream, int dtype, const void *value, const int64_t *spatial_shapes,
+                              const int64_t *level_start, const float *sampling_loc, const float *attn_weight,
+                              int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                              int num_point, void *out);
+size_t semidetr_msda_backward_h16_workspace_bytes(int batch, int spatial_size, int num_heads, int channels);
+int semidetr_msda_backward_h16(void *stream, int dtype, const void *grad_out, const void *value,
+                               const int64_t *spatial_shapes, const int64_t *level_start, const float *sampling_loc,
+                               const float *attn_weight, int batch, int spatial_size, int num_heads, int channels,
+                               int num_levels, int num_query, int num_point, void *workspace, void *grad_value,
+                               float *grad_sampling_loc, float *grad_attn_weight);
+const char *semidetr_msda_h16_last_kernels(void);
+
+/* ---------------------------------------------------------------------------------------------
  * Hungarian matcher: cost matrix + linear sum assignment + assignment scatter, batched and
  * device-resident (no host round trip inside).
  *

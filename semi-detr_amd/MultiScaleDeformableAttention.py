@@ -11,6 +11,11 @@ re-exports its functions; there is no Python or CPU implementation to fall back 
     ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
                             im2col_step) -> [grad_value, grad_sampling_loc, grad_attn_weight]
     ms_deform_attn_fused_forward / ms_deform_attn_fused_backward / fused_supported   
+    ms_deform_attn_h16_forward(value16, spatial_shapes, level_start_index, sampling_loc_f32, attn_weight_f32[, im2col_step])
+                                                                      -> Tensor of value's dtype (Half / BFloat16)
+    ms_deform_attn_h16_backward(value16, spatial_shapes, level_start_index, sampling_loc_f32, attn_weight_f32, grad_output16
+                                [, im2col_step]) -> [grad_value (value's dtype), grad_sampling_loc (fp32), grad_attn_weight (fp32)]
+    h16_supported(value, sampling_loc, attn_weight) -> the mixed-precision op takes these tensors
     pyramid_check(spatial_shapes, level_start_index, S) -> bit 0: sum(H*W) == S, bit 1: exact tiling (cached)
     mask_extents(padding_mask, spatial_shapes, level_start_index) -> (N, L) int32 summary of a padding mask (cached; the
                                                                       fused calls fetch it themselves)
@@ -35,6 +40,9 @@ ms_deform_attn_backward = _msda_ext.ms_deform_attn_backward
 ms_deform_attn_fused_forward = _msda_ext.ms_deform_attn_fused_forward
 ms_deform_attn_fused_backward = _msda_ext.ms_deform_attn_fused_backward
 fused_supported = _msda_ext.fused_supported
+ms_deform_attn_h16_forward = _msda_ext.ms_deform_attn_h16_forward
+ms_deform_attn_h16_backward = _msda_ext.ms_deform_attn_h16_backward
+h16_supported = _msda_ext.h16_supported
 pyramid_check = _msda_ext.pyramid_check
 mask_extents = _msda_ext.mask_extents
 gather_choice = _msda_ext.gather_choice

@@ -209,6 +209,96 @@ std::vector<at::Tensor> ms_deform_attn_backward(const at::Tensor &value, const a
     return {gv, gl, ga};
 }
 
+// ---- fp16 / bf16 value maps (not part of the reference's pybind surface): what autocast hands MSDeformAttn, without the fp32
+// copies of the reference's "for amp" branch (ops/modules/ms_deform_attn.py:113-120).  value / grad_output / out / grad_value
+// are Half or BFloat16, locations and weights (and their gradients) Float; include/semidetr_hip.h states the contract.
+bool h16_supported(const at::Tensor &value, const at::Tensor &loc, const at::Tensor &attn)
+{
+    return value.is_cuda() && (value.scalar_type() == at::kHalf || value.scalar_type() == at::kBFloat16) && value.dim() == 4 &&
+           loc.scalar_type() == at::kFloat && attn.scalar_type() == at::kFloat;
+}
+
+Dims h16_dims(const at::Tensor &value, const at::Tensor &shapes, const at::Tensor &starts, const at::Tensor &loc,
+              const at::Tensor &attn, int64_t im2col_step, const char *what)
+{
+    TORCH_CHECK(value.is_cuda(), "Not implemented on the CPU");
+    check_tensor(value, value, "value");
+    check_tensor(shapes, value, "spatial_shapes");
+    check_tensor(starts, value, "level_start_index");
+    check_tensor(loc, value, "sampling_loc");
+    check_tensor(attn, value, "attn_weight");
+    TORCH_CHECK(value.dim() == 4 && loc.dim() == 6 && attn.dim() == 5, what,
+                ": expected value (N,S,M,D), sampling_loc (N,Lq,M,L,P,2), attn_weight (N,Lq,M,L,P)");
+    Dims d;
+    d.N = (int)value.size(0); d.S = (int)value.size(1); d.M = (int)value.size(2); d.D = (int)value.size(3);
+    d.L = (int)shapes.size(0); d.Lq = (int)loc.size(1); d.P = (int)loc.size(4);
+    const int64_t step = std::min<int64_t>(d.N, im2col_step);
+    TORCH_CHECK(step > 0 && d.N % step == 0, "batch(", d.N, ") must divide im2col_step(", step, ")");
+    TORCH_CHECK(shapes.scalar_type() == at::kLong, "expected scalar type Long for spatial_shapes");
+    TORCH_CHECK(starts.scalar_type() == at::kLong, "expected scalar type Long for level_start_index");
+    TORCH_CHECK(value.scalar_type() != at::kFloat && value.scalar_type() != at::kDouble, what, ": value is '",
+                scalar_name(value.scalar_type()), "' -- the fp32 / fp64 entry is ms_deform_attn_forward / ms_deform_attn_backward");
+    TORCH_CHECK(value.scalar_type() == at::kHalf || value.scalar_type() == at::kBFloat16, "\"", what, "\" not implemented for '",
+                scalar_name(value.scalar_type()), "'");
+    TORCH_CHECK(loc.scalar_type() == at::kFloat && attn.scalar_type() == at::kFloat, what,
+                ": sampling_loc and attn_weight must be Float (locations and weights are never narrowed to 16 bits), got '",
+                scalar_name(loc.scalar_type()), "' and '", scalar_name(attn.scalar_type()), "'");
+    TORCH_CHECK(loc.size(0) == d.N && loc.size(2) == d.M && loc.size(3) == d.L && loc.size(5) == 2 &&
+                    attn.size(0) == d.N && attn.size(1) == d.Lq && attn.size(2) == d.M && attn.size(3) == d.L &&
+                    attn.size(4) == d.P && starts.numel() == d.L && shapes.dim() == 2 && shapes.size(1) == 2,
+                what, ": inconsistent tensor shapes");
+    return d;
+}
+
+int h16_dtype(const at::Tensor &value) { return value.scalar_type() == at::kHalf ? SEMIDETR_H16_FP16 : SEMIDETR_H16_BF16; }
+
+at::Tensor ms_deform_attn_h16_forward(const at::Tensor &value, const at::Tensor &spatial_shapes,
+                                      const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
+                                      const at::Tensor &attn_weight, int64_t im2col_step)
+{
+    const Dims d = h16_dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step,
+                            "ms_deform_attn_h16_forward");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
+    at::Tensor out = at::empty({d.N, d.Lq, (int64_t)d.M * d.D}, value.options());      // the kernel writes all of it
+    if (out.numel() == 0 || value.numel() == 0) return out.zero_();
+    const int rc = semidetr_msda_forward_h16(stream_of(value), h16_dtype(value), value.data_ptr(), spatial_shapes.data_ptr<int64_t>(),
+                                             level_start_index.data_ptr<int64_t>(), sampling_loc.data_ptr<float>(),
+                                             attn_weight.data_ptr<float>(), d.N, d.S, d.M, d.D, d.L, d.Lq, d.P, out.data_ptr());
+    check_rc(rc, "ms_deform_attn_h16_forward");
+    return out;
+}
+
+std::vector<at::Tensor> ms_deform_attn_h16_backward(const at::Tensor &value, const at::Tensor &spatial_shapes,
+                                                    const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
+                                                    const at::Tensor &attn_weight, const at::Tensor &grad_output,
+                                                    int64_t im2col_step)
+{
+    const Dims d = h16_dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step,
+                            "ms_deform_attn_h16_backward");
+    check_tensor(grad_output, value, "grad_output");
+    TORCH_CHECK(grad_output.scalar_type() == value.scalar_type(), "ms_deform_attn_h16_backward: value ('",
+                scalar_name(value.scalar_type()), "') and grad_output ('", scalar_name(grad_output.scalar_type()),
+                "') must share one dtype");
+    TORCH_CHECK(grad_output.numel() == (int64_t)d.N * d.Lq * d.M * d.D,
+                "ms_deform_attn_h16_backward: grad_output must be (N, Lq, M*D)");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
+    at::Tensor gv = at::empty_like(value);            // every element written by the conversion kernel
+    at::Tensor gl = at::empty_like(sampling_loc);     // fully written by the kernels
+    at::Tensor ga = at::empty_like(attn_weight);
+    if (value.numel() == 0 || gl.numel() == 0) return {gv.zero_(), gl.zero_(), ga.zero_()};
+    // grad_value is summed in fp32 and rounded once: the sums live in this workspace, cleared on the current stream
+    at::Tensor ws = at::empty({(int64_t)(semidetr_msda_backward_h16_workspace_bytes(d.N, d.S, d.M, d.D) / sizeof(float))},
+                              value.options().dtype(at::kFloat));
+    ws.zero_();
+    const int rc = semidetr_msda_backward_h16(stream_of(value), h16_dtype(value), grad_output.data_ptr(), value.data_ptr(),
+                                              spatial_shapes.data_ptr<int64_t>(), level_start_index.data_ptr<int64_t>(),
+                                              sampling_loc.data_ptr<float>(), attn_weight.data_ptr<float>(), d.N, d.S, d.M, d.D,
+                                              d.L, d.Lq, d.P, ws.data_ptr(), gv.data_ptr(), gl.data_ptr<float>(),
+                                              ga.data_ptr<float>());
+    check_rc(rc, "ms_deform_attn_h16_backward");
+    return {gv, gl, ga};
+}
+
 // ---- fused prologue / epilogue (not part of the reference's pybind surface) ----------------------------------
 bool fused_supported(const at::Tensor &value, const at::Tensor &ref, const at::Tensor &off, const at::Tensor &logits)
 {
@@ -401,6 +491,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("level_start_index"), py::arg("reference_points"), py::arg("sampling_offsets"), py::arg("attn_logits"),
           py::arg("grad_output"), py::arg("padding_mask") = py::none(), py::arg("policy_slot") = 0);
     m.def("fused_supported", &fused_supported);
+    // fp16 / bf16 value maps with fp32 locations and weights (include/semidetr_hip.h: semidetr_msda_forward_h16)
+    m.def("ms_deform_attn_h16_forward", &ms_deform_attn_h16_forward, py::arg("value"), py::arg("spatial_shapes"),
+          py::arg("level_start_index"), py::arg("sampling_loc"), py::arg("attn_weight"), py::arg("im2col_step") = 64);
+    m.def("ms_deform_attn_h16_backward", &ms_deform_attn_h16_backward, py::arg("value"), py::arg("spatial_shapes"),
+          py::arg("level_start_index"), py::arg("sampling_loc"), py::arg("attn_weight"), py::arg("grad_output"),
+          py::arg("im2col_step") = 64);
+    m.def("h16_supported", &h16_supported, py::arg("value"), py::arg("sampling_loc"), py::arg("attn_weight"),
+          "value is a 16-bit (Half / BFloat16) CUDA map and locations / weights are Float: the mixed-precision op takes the call");
     m.def("gather_choice", [](int64_t slot) { return semidetr_msda_gather_choice((int)slot); }, py::arg("policy_slot") = 0,
           "What an encoder backward of this slot issued now would pick for grad_sampling_loc / grad_attn_weight (SEMIDETR_MSDA_GATHER_WINDOW "
           "or _PATCH): OR it into the backward call's policy_slot and the backward follows what was known at forward time.");

@@ -40,6 +40,31 @@ class MSDeformAttnFunction(Function):
         return (grad_value, None, None, grad_sampling_loc, grad_attn_weight, None, None)[:len(ctx.needs_input_grad)]
 
 
+class MSDeformAttnMixedFunction(Function):
+    """The operator on a 16-bit value map (torch.autocast, or an all-fp16 module): ``apply(value16, value_spatial_shapes,
+    value_level_start_index, sampling_locations_f32, attention_weights_f32, im2col_step)``.  ``value16`` is fp16 or bf16 and so are
+    the output and ``grad_value``; locations, weights and their gradients are fp32; all arithmetic is fp32 and the two 16-bit
+    results are rounded once (include/semidetr_hip.h: semidetr_msda_forward_h16).  The 16-BIT value is what is saved for the
+    backward: half the saved-activation memory of ``MSDeformAttnFunction`` on ``value.float()``."""
+
+    @staticmethod
+    def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights, im2col_step):
+        ctx.im2col_step = im2col_step
+        output = MSDA.ms_deform_attn_h16_forward(value, value_spatial_shapes, value_level_start_index, sampling_locations,
+                                                 attention_weights, ctx.im2col_step)
+        ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        value, spatial_shapes, level_start_index, sampling_locations, attention_weights = ctx.saved_tensors
+        grad_value, grad_sampling_loc, grad_attn_weight = MSDA.ms_deform_attn_h16_backward(
+            value, spatial_shapes, level_start_index, sampling_locations, attention_weights,
+            grad_output.contiguous(), ctx.im2col_step)
+        return grad_value, None, None, grad_sampling_loc, grad_attn_weight, None
+
+
 class MSDeformAttnFusedFunction(Function):
     """MSDeformAttn.forward between the Linear layers as ONE op: consumes the
     reference points, the raw sampling offsets and the raw attention logits; softmax, location arithmetic

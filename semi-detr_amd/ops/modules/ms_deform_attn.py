@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ... import MultiScaleDeformableAttention as MSDA
-from ..functions import MSDeformAttnFunction, MSDeformAttnFusedFunction
+from ..functions import MSDeformAttnFunction, MSDeformAttnFusedFunction, MSDeformAttnMixedFunction
 
 
 def _is_power_of_2(n):
@@ -30,6 +30,24 @@ _policy_slots = itertools.count(1)
 
 def _next_policy_slot():
     return (next(_policy_slots) - 1) % 255 + 1
+
+
+# Which 16-bit calls stay on the up-cast route (value.float() -> fp32 op -> .to(dtype)): the shape classes on which the
+# mixed-precision kernels measured SLOWER than it by more than the spread between rounds (tools/msda_h16_probe.py,
+# profiles/msda_h16_probe.txt; fp16 and bf16 alike).
+#   * no backward will follow (no_grad / nothing requires grad: the teacher, evaluation): the 16-bit forward is no slower on any
+#     shape measured (encoder 1.00-1.05x, decoder 2.3x, micro-benchmark 2.8x) -> every call takes it;
+#   * a backward follows, the queries are the pixels (encoder self-attention): the fp32 op scatters grad_value with its
+#     region-owned kernels, the 16-bit backward with row atomics -- 4.5 against 0.77 ms at bs 4 -> up-cast route;
+#   * a backward follows, any other query set: level at 600 (n, q) rows, behind from _H16_TRAIN_MAX_ROWS rows on (the fp32 op's
+#     merged level scatter) -> up-cast route above that.
+_H16_TRAIN_MAX_ROWS = 600
+
+
+def _h16_takes_upcast_route(queries_are_pixels, rows, backward_follows):
+    if not backward_follows:
+        return False
+    return bool(queries_are_pixels) or rows > _H16_TRAIN_MAX_ROWS
 
 
 class MSDeformAttn(nn.Module):
@@ -47,6 +65,10 @@ class MSDeformAttn(nn.Module):
         # intermediates in HBM.  Not a parameter / buffer -> state_dict is unchanged.  Set False for the
         # reference's op-by-op sequence.
         self.fuse_prologue = True
+        # A 16-bit value map (torch.autocast, or the module after .half() / .bfloat16()) goes to the mixed-precision kernels as it
+        # is: 16-bit value / output / grad_value, fp32 locations and weights, fp32 arithmetic.  False restores the
+        # up-cast route (value.float() -> the fp32 op -> .to(dtype)).  Plain attribute like fuse_prologue, not in state_dict.
+        self.native_16bit = True
         # Which of the two encoder forward kernels runs follows how far THIS instance's learned offsets reach (semidetr_hip.h:
         # SEMIDETR_MSDA_POLICY_SLOT): instances take consecutive slots 1..255 (the reference builds 12 per model,
         # transformer.py:609,760; beyond 255 instances slots are shared, which only mixes their counts).  Plain attribute.
@@ -66,6 +88,7 @@ class MSDeformAttn(nn.Module):
         super().__setstate__(state)
         self.__dict__["policy_slot"] = _next_policy_slot()
         self.__dict__.setdefault("fuse_prologue", True)
+        self.__dict__.setdefault("native_16bit", True)
 
     def _reset_parameters(self):
         # ms_deform_attn.py:62-76 -- head m looks along direction 2*pi*m/M, point i at distance i+1
@@ -125,10 +148,23 @@ class MSDeformAttn(nn.Module):
             raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead."
                              .format(reference_points.shape[-1]))
 
-        if value.dtype == torch.float16:      # amp: the op itself runs in fp32 (ms_deform_attn.py:114-120)
+        if value.dtype in (torch.float16, torch.bfloat16):      # amp (ms_deform_attn.py:114-120)
+            # Locations and weights are formed exactly as before and go in as fp32 (they already are under autocast; an all-fp16
+            # module up-casts them as before); value goes in as it is and the op's output goes to output_proj in value's dtype.
+            # The only difference from the up-cast route's results is the fp32 summation order before the ONE rounding of the
+            # output and of grad_value; bf16 never ran on the up-cast route's fp32 entry points at all.
+            loc32, w32 = locations.float().contiguous(), weights.float().contiguous()
+            follows = torch.is_grad_enabled() and (value.requires_grad or loc32.requires_grad or w32.requires_grad)
+            pixels = Len_q == Len_in and bool(MSDA.pyramid_check(input_spatial_shapes, input_level_start_index, Len_in) & 2)
+            if getattr(self, "native_16bit", True) and MSDA.h16_supported(value, loc32, w32) \
+                    and not _h16_takes_upcast_route(pixels, N * Len_q, follows):
+                output = MSDeformAttnMixedFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index,
+                                                         loc32, w32, self.im2col_step)
+                return self.output_proj(output)
+            # the up-cast route: the op itself runs in fp32 on a copy of the value map
             output = MSDeformAttnFunction.apply(value.float(), input_spatial_shapes, input_level_start_index,
-                                                locations.float(), weights.float(), self.im2col_step, getattr(self, "policy_slot", 0))
-            return self.output_proj(output.to(torch.float16))
+                                                loc32, w32, self.im2col_step, getattr(self, "policy_slot", 0))
+            return self.output_proj(output.to(value.dtype))
         output = MSDeformAttnFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index,
                                             locations.contiguous(), weights.contiguous(), self.im2col_step, getattr(self, "policy_slot", 0))
         return self.output_proj(output)
