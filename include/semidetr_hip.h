@@ -735,6 +735,46 @@ int semidetr_consis_loss_forward_f32(void *stream, const semidetr_consis_loss *p
 int semidetr_consis_loss_backward_f32(void *stream, const semidetr_consis_loss *params /* host */, const void *workspace,
                                       size_t workspace_bytes, const float *grad_losses);
 
+/* ---------------------------------------------------------------------------------------------
+ * Decoder self-attention core (ABI 7, additive): out = softmax(scale * Q K^T + mask) V and its backward, head dimension 32.
+ *
+ * Replaces  the attention between the two projections of `self.self_attn(q, k, tgt, attn_mask=self_attn_mask)[0]`
+ *           detr_od/models/utils/transformer.py:975-1039 (nn.MultiheadAttention: bmm, mask add, softmax, bmm, head average)
+ *
+ * fp32 in / arithmetic / out, on `stream`, no host synchronisation, no memset, no float atomics; bitwise reproducible.  The
+ * parameter block is read on the host during the call.  q (len_q, batch, heads * 32) and k, v (len_k, batch, heads * 32) are
+ * read through their (length, batch) strides in ELEMENTS; the last dimension has stride 1, every row starts 16-byte aligned
+ * (base aligned, strides multiples of 4), so the three may be slices of one in-projection output.  out (len_q, batch,
+ * heads * 32) and grad_out are contiguous; lse (batch, heads, len_q) is the row log-sum-exp the forward writes and the backward
+ * reads.  mask is NULL or (len_q, len_k) bytes, non-zero = blocked, shared by images and heads.  32 x 32 tiles of the mask are
+ * classed by one small launch: a tile blocked everywhere is skipped, a tile open everywhere reads no mask byte.  A row with
+ * every key blocked is NaN in out; its backward is outside the contract.  head_dim != 32 is SEMIDETR_E_BADARG.
+ *
+ * semidetr_self_attn_forward_f32  -- two launches (one without a mask): writes out and lse.
+ * semidetr_self_attn_backward_f32 -- three launches at most (tile classes; delta = rowsum(dO * O) and dQ; dK and dV).
+ *   grad_q / grad_k / grad_v may each be NULL (not computed; at least one is not); they are written through their own
+ *   (length, batch) strides, every element of every row.
+ * workspace: semidetr_self_attn_workspace_bytes(batch, heads, len_q, len_k) bytes, 16-byte aligned, no initialisation; the
+ *   backward may use another one than the forward.
+ * Limits: batch * heads <= 65535, len_q and len_k < 2^24.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct semidetr_self_attn {
+    int batch, heads, head_dim, len_q, len_k;
+    float scale;
+    const float *q, *k, *v;
+    int64_t q_stride[2], k_stride[2], v_stride[2];        /* (length, batch) strides in elements */
+    const uint8_t *mask;                                  /* (len_q, len_k) or NULL */
+    float *out, *lse;                                     /* forward: written; backward: read */
+    const float *grad_out;                                /* backward only from here on */
+    float *grad_q, *grad_k, *grad_v;
+    int64_t gq_stride[2], gk_stride[2], gv_stride[2];
+} semidetr_self_attn;
+size_t semidetr_self_attn_workspace_bytes(int batch, int heads, int len_q, int len_k);
+int semidetr_self_attn_forward_f32(void *stream, const semidetr_self_attn *params /* host */, void *workspace,
+                                   size_t workspace_bytes);
+int semidetr_self_attn_backward_f32(void *stream, const semidetr_self_attn *params /* host */, void *workspace,
+                                    size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

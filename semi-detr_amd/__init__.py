@@ -29,6 +29,8 @@ from .dn_query import consistency_queries, prepare_for_cdn, prepare_for_cdn_plus
 from .query_select import gen_encoder_output_proposals, select_queries, two_stage_queries  # noqa: E402,F401
 from .detect import PendingDetections, detection_results, get_bboxes  # noqa: E402,F401
 from .consis_loss import ConsistencyLossFunction, consistency_loss  # noqa: E402,F401
+from .self_attn import (MaskedAttentionFunction, MultiheadAttention, convert_self_attention,  # noqa: E402,F401
+                        masked_attention)
 from .pseudo_label import (filter_pseudo_labels, get_bboxes_for_pseudo_label, teacher_pseudo_labels,  # noqa: E402,F401
                            transform_bboxes)
 
@@ -39,4 +41,5 @@ __all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttnMix
            "fit_gmm_threshold_segments", "unsup_gmm_filter", "GmmFilterResult", "PendingGmmFilter",
            "FocalLoss", "SetLossSegment", "loss_set", "set_losses", "prepare_for_cdn", "prepare_for_cdn_plus",
            "prepare_unsup_cdn", "consistency_queries", "gen_encoder_output_proposals", "select_queries", "two_stage_queries",
-           "get_bboxes", "detection_results", "PendingDetections", "consistency_loss", "ConsistencyLossFunction"]
+           "get_bboxes", "detection_results", "PendingDetections", "consistency_loss", "ConsistencyLossFunction",
+           "masked_attention", "MaskedAttentionFunction", "MultiheadAttention", "convert_self_attention"]

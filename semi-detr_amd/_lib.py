@@ -93,6 +93,10 @@ SIGNATURES = {
     "semidetr_consis_loss_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
     "semidetr_consis_loss_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
     "semidetr_consis_loss_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    # decoder self-attention core (self_attn.py); the parameter block (semidetr_self_attn, self_attn._Params) is a host pointer
+    "semidetr_self_attn_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
+    "semidetr_self_attn_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
+    "semidetr_self_attn_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so

@@ -104,3 +104,32 @@ def bind_query_select():
     m.gen_encoder_output_proposals = query_select.gen_encoder_output_proposals
     m.DINOTransformer.two_stage_queries = query_select.two_stage_queries
     return names, []
+
+
+def bind_decoder_self_attention():
+    """Where ``detr_od`` is importable, wrap the decoder layer's ``__init__`` (``DINOTransformerDecoderLayer``,
+    transformer.py:747-765; ``DeformableTransformerDecoderLayer`` in trees that keep DINO's own name) so that every layer built
+    from then on has its ``nn.MultiheadAttention`` replaced by ``semi_detr_amd.MultiheadAttention``
+    (``self_attn.convert_self_attention``: same parameters, same ``state_dict`` keys).  Returns (bound, skipped) names."""
+    import functools
+    import importlib
+
+    from .self_attn import convert_self_attention
+    layers = ("DINOTransformerDecoderLayer", "DeformableTransformerDecoderLayer")
+    try:
+        m = importlib.import_module("detr_od.models.utils.transformer")
+    except ImportError:
+        return [], [layers[0] + ".self_attn"]
+    cls = next((getattr(m, n) for n in layers if hasattr(m, n)), None)
+    if cls is None:
+        return [], [layers[0] + ".self_attn"]
+    names = [cls.__name__ + ".self_attn"]
+    init = cls.__init__
+    if not getattr(init, "_semidetr_self_attn", False):
+        @functools.wraps(init)
+        def wrapped(self, *args, **kwargs):
+            init(self, *args, **kwargs)
+            convert_self_attention(self)
+        wrapped._semidetr_self_attn = True
+        cls.__init__ = wrapped
+    return names, []

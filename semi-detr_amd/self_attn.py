@@ -1,0 +1,282 @@
+"""Decoder self-attention on the MI355X (``csrc/self_attn.hip``): the dense attention of ``DINOTransformerDecoderLayer``
+(detr_od/models/utils/transformer.py:765, 793-816), ``self.self_attn(q, k, tgt, attn_mask=self_attn_mask)[0]``.
+
+``masked_attention(q, k, v, num_heads, attn_mask=None, scale=None)`` is the core ``softmax(scale * q k^T + mask) v`` on seq-first
+``(L, B, E)`` tensors: forward two launches (one without a mask), backward three at most, on the current stream, with no host
+synchronisation and no ``.item()``.  The ``(Lq, Lk)`` scores never reach memory; the op saves its inputs, ``out`` and the row
+log-sum-exp ``(B, H, Lq)``.  ``q``, ``k`` and ``v`` are read through their first two strides (last stride 1, rows 16-byte
+aligned, copied only where they are not), so slices of one in-projection output are read in place.  ``attn_mask`` is torch's
+bool ``(Lq, Lk)`` mask, ``True`` = blocked; the mask that ``dn_query`` writes is block-structured and its fully blocked 32 x 32
+tiles are skipped.  A row with every key blocked is NaN, as in torch.
+
+``MultiheadAttention`` is the drop-in for the layer's ``nn.MultiheadAttention`` (same parameter names and shapes, so a
+reference ``state_dict`` loads with ``strict=True``); the two projections stay GEMMs.  ``convert_self_attention(module)``
+replaces the qualifying ``nn.MultiheadAttention`` children of a built model in place, adopting their ``Parameter`` objects.
+
+Not built: float and 3-D masks, ``key_padding_mask``, attention dropout, head dimensions other than 32,
+16-bit inputs (they are computed in fp32) and the head-averaged attention weights.
+"""
+import ctypes
+
+import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
+from torch.nn import functional as F
+
+from . import _lib
+
+HEAD_DIM = 32
+
+
+class _Params(ctypes.Structure):
+    """Mirror of ``semidetr_self_attn`` (include/semidetr_hip.h)."""
+    _fields_ = [("batch", ctypes.c_int), ("heads", ctypes.c_int), ("head_dim", ctypes.c_int), ("len_q", ctypes.c_int),
+                ("len_k", ctypes.c_int), ("scale", ctypes.c_float),
+                ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("q_stride", ctypes.c_int64 * 2), ("k_stride", ctypes.c_int64 * 2), ("v_stride", ctypes.c_int64 * 2),
+                ("mask", ctypes.c_void_p), ("out", ctypes.c_void_p), ("lse", ctypes.c_void_p), ("grad_out", ctypes.c_void_p),
+                ("grad_q", ctypes.c_void_p), ("grad_k", ctypes.c_void_p), ("grad_v", ctypes.c_void_p),
+                ("gq_stride", ctypes.c_int64 * 2), ("gk_stride", ctypes.c_int64 * 2), ("gv_stride", ctypes.c_int64 * 2)]
+
+
+def _rows(t):
+    """A ``(L, B, E)`` tensor as the kernel reads it: fp32, last stride 1, every row 16-byte aligned; copied only where not."""
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(2) != 1 or t.data_ptr() % 16 or t.stride(0) % 4 or t.stride(1) % 4:
+        t = t.contiguous()
+    return t
+
+
+def _split(x, y, z, packed_qk):
+    if not packed_qk:
+        return x, y, z
+    E = y.shape[2]
+    return x[..., :E], x[..., E:], y
+
+
+def _params(q, k, v, mask, heads, scale):
+    p = _Params()
+    (Lq, B, E), Lk = q.shape, k.shape[0]
+    p.batch, p.heads, p.head_dim, p.len_q, p.len_k, p.scale = B, heads, E // heads, Lq, Lk, scale
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        setattr(p, name, t.data_ptr())
+        st = getattr(p, name + "_stride")
+        st[0], st[1] = t.stride(0), t.stride(1)
+    p.mask = mask.data_ptr() if mask is not None else None
+    return p
+
+
+def _workspace(p, dev):
+    nbytes = _lib.lib().semidetr_self_attn_workspace_bytes(p.batch, p.heads, p.len_q, p.len_k)
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
+
+
+class MaskedAttentionFunction(torch.autograd.Function):
+    """``apply(x, y, z, mask, num_heads, scale, packed_qk)`` -> ``out (Lq, B, E)``.  ``packed_qk`` false: ``x, y, z`` are
+    ``q, k, v``.  True: ``x`` is the ``(L, B, 2E)`` output of one GEMM that holds ``[q | k]``, ``y`` is ``v`` and ``z`` is
+    ``None``; the backward then writes ``dq`` and ``dk`` side by side into ONE gradient buffer for ``x``, so autograd adds no
+    slice-backward copies.  ``mask``: ``None`` or a contiguous ``(Lq, Lk)`` uint8 tensor, non-zero = blocked."""
+
+    @staticmethod
+    def forward(ctx, x, y, z, mask, num_heads, scale, packed_qk):
+        q, k, v = (_rows(t) for t in _split(x, y, z, packed_qk))
+        dev = q.device
+        p = _params(q, k, v, mask, num_heads, scale)
+        out = torch.empty(q.shape, dtype=torch.float32, device=dev)
+        lse = torch.empty((p.batch, num_heads, p.len_q), dtype=torch.float32, device=dev)
+        p.out, p.lse = out.data_ptr(), lse.data_ptr()
+        work, nbytes = _workspace(p, dev)
+        _lib.call("semidetr_self_attn_forward_f32", dev, ctypes.byref(p), work, nbytes)
+        ctx.num_heads, ctx.scale, ctx.packed_qk = num_heads, scale, packed_qk
+        ctx.dtypes = [t.dtype if t is not None else None for t in (x, y, z)]
+        ctx.save_for_backward(x, y, z, mask, out, lse)
+        result = out if x.dtype == torch.float32 else out.to(x.dtype)
+        return result
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, y, z, mask, out, lse = ctx.saved_tensors
+        need = ctx.needs_input_grad[:3]
+        if not any(need):
+            return (None,) * 7
+        q, k, v = (_rows(t) for t in _split(x, y, z, ctx.packed_qk))
+        dev = q.device
+        g = g.detach()
+        if g.dtype != torch.float32:
+            g = g.float()
+        g = g.contiguous()
+        p = _params(q, k, v, mask, ctx.num_heads, ctx.scale)
+        p.out, p.lse, p.grad_out = out.data_ptr(), lse.data_ptr(), g.data_ptr()
+        if ctx.packed_qk:
+            need_q = need_k = need[0]
+            need_v = need[1]
+            gx = torch.empty(x.shape, dtype=torch.float32, device=dev) if need[0] else None
+            E = y.shape[2]
+            gq, gk = (gx[..., :E], gx[..., E:]) if need[0] else (None, None)
+        else:
+            need_q, need_k, need_v = need
+            gq = torch.empty(q.shape, dtype=torch.float32, device=dev) if need_q else None
+            gk = torch.empty(k.shape, dtype=torch.float32, device=dev) if need_k else None
+        gv = torch.empty(v.shape, dtype=torch.float32, device=dev) if need_v else None
+        for name, t in (("q", gq), ("k", gk), ("v", gv)):
+            if t is not None:
+                setattr(p, "grad_" + name, t.data_ptr())
+                st = getattr(p, "g" + name + "_stride")
+                st[0], st[1] = t.stride(0), t.stride(1)
+        work, nbytes = _workspace(p, dev)
+        _lib.call("semidetr_self_attn_backward_f32", dev, ctypes.byref(p), work, nbytes)
+
+        def cast(t, dt):
+            return t if t is None or t.dtype == dt else t.to(dt)
+        if ctx.packed_qk:
+            return cast(gx, ctx.dtypes[0]), cast(gv, ctx.dtypes[1]), None, None, None, None, None
+        return cast(gq, ctx.dtypes[0]), cast(gk, ctx.dtypes[1]), cast(gv, ctx.dtypes[2]), None, None, None, None
+
+
+def _byte_mask(attn_mask, Lq, Lk, dev):
+    """torch's bool ``attn_mask`` as the kernel's ``(Lq, Lk)`` byte matrix (a view where it is contiguous)."""
+    if attn_mask is None:
+        return None
+    if attn_mask.dim() != 2:
+        raise NotImplementedError(f"masked_attention: attn_mask is (Lq, Lk), got {attn_mask.dim()} dimensions "
+                                  "(per-head masks are not built)")
+    if attn_mask.dtype not in (torch.bool, torch.uint8):
+        raise NotImplementedError(f"masked_attention: attn_mask is a bool mask, got {attn_mask.dtype} (float masks are not built)")
+    if tuple(attn_mask.shape) != (Lq, Lk):
+        raise ValueError(f"masked_attention: attn_mask is {tuple(attn_mask.shape)}, expected {(Lq, Lk)}")
+    if attn_mask.device != dev:
+        raise RuntimeError("masked_attention: attn_mask must live on the GPU of q (no CPU fallback)")
+    m = attn_mask.detach().contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _check(q, k, v, num_heads):
+    for t, what in ((q, "q"), (k, "k"), (v, "v")):
+        if t.dim() != 3:
+            raise ValueError(f"masked_attention: {what} is (L, B, E), got {tuple(t.shape)}")
+    Lq, B, E = q.shape
+    if k.shape[1:] != (B, E) or v.shape != k.shape:
+        raise ValueError(f"masked_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit")
+    if E != num_heads * HEAD_DIM:
+        raise NotImplementedError(f"masked_attention: head dimension {E / num_heads:g} (E = {E}, {num_heads} heads); only "
+                                  f"{HEAD_DIM} is built")
+    if Lq == 0 or k.shape[0] == 0 or B == 0:
+        raise ValueError("masked_attention: empty q / k")
+    for t, what in ((q, "q"), (k, "k"), (v, "v")):
+        if not t.is_cuda:
+            raise RuntimeError(f"masked_attention: {what} must live on the GPU (no CPU fallback)")
+
+
+def masked_attention(q, k, v, num_heads, attn_mask=None, scale=None):
+    """``softmax(scale * q k^T + attn_mask) v`` per image and head (module docstring): ``q (Lq, B, E)``, ``k, v (Lk, B, E)`` ->
+    ``(Lq, B, E)``, ``E = num_heads * 32``.  ``scale`` defaults to ``32 ** -0.5``."""
+    mask = _byte_mask(attn_mask, q.shape[0], k.shape[0], q.device)
+    _check(q, k, v, num_heads)
+    scale = HEAD_DIM ** -0.5 if scale is None else float(scale)
+    return MaskedAttentionFunction.apply(q, k, v, mask, num_heads, scale, False)
+
+
+class MultiheadAttention(nn.Module):
+    """Drop-in for the decoder layer's ``nn.MultiheadAttention(embed_dim, num_heads, dropout=0.0)``: the same parameters
+    (``in_proj_weight (3E, E)``, ``in_proj_bias (3E)``, ``out_proj.weight``, ``out_proj.bias``) under the same names and the
+    same ``_reset_parameters``; seq-first ``(L, B, E)`` tensors.
+
+    ``forward`` returns ``(out, None)``: the reference takes ``[0]`` and never reads the head-averaged attention weights
+    (transformer.py:810), so they are not computed whatever ``need_weights`` says.  With ``query is key`` (the layer's
+    ``q = k = tgt + pos``) the in-projection is one GEMM for ``[q | k]`` and one for ``v``."""
+
+    def __init__(self, embed_dim, num_heads, dropout=0.0, bias=True, add_bias_kv=False, add_zero_attn=False, kdim=None,
+                 vdim=None, batch_first=False):
+        super().__init__()
+        if add_bias_kv or add_zero_attn or batch_first:
+            raise NotImplementedError("MultiheadAttention: add_bias_kv, add_zero_attn and batch_first are not built")
+        if (kdim is not None and kdim != embed_dim) or (vdim is not None and vdim != embed_dim):
+            raise NotImplementedError("MultiheadAttention: kdim / vdim other than embed_dim are not built")
+        if embed_dim != num_heads * HEAD_DIM:
+            raise NotImplementedError(f"MultiheadAttention: head dimension {embed_dim / num_heads:g}; only {HEAD_DIM} is built")
+        self.embed_dim, self.num_heads, self.dropout, self.head_dim = embed_dim, num_heads, float(dropout), HEAD_DIM
+        self.batch_first = False
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        if bias:
+            self.in_proj_bias = nn.Parameter(torch.empty(3 * embed_dim))
+        else:
+            self.register_parameter("in_proj_bias", None)
+        self.out_proj = nn.Linear(embed_dim, embed_dim, bias=bias)
+        self._reset_parameters()
+
+    def _reset_parameters(self):
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        if self.in_proj_bias is not None:
+            nn.init.constant_(self.in_proj_bias, 0.)
+            nn.init.constant_(self.out_proj.bias, 0.)
+
+    @classmethod
+    def adopt(cls, mha):
+        """The mirror of a built ``nn.MultiheadAttention`` that holds the SAME ``Parameter`` objects (and ``out_proj`` module)."""
+        reason = _why_not(mha)
+        if reason:
+            raise NotImplementedError(f"MultiheadAttention: {reason}")
+        new = cls.__new__(cls)
+        nn.Module.__init__(new)
+        new.embed_dim, new.num_heads, new.dropout, new.head_dim = mha.embed_dim, mha.num_heads, float(mha.dropout), HEAD_DIM
+        new.batch_first = False
+        new.in_proj_weight = mha.in_proj_weight
+        if mha.in_proj_bias is not None:
+            new.in_proj_bias = mha.in_proj_bias
+        else:
+            new.register_parameter("in_proj_bias", None)
+        new.out_proj = mha.out_proj
+        new.train(mha.training)
+        return new
+
+    def forward(self, query, key, value, attn_mask=None, need_weights=True, key_padding_mask=None):
+        if key_padding_mask is not None:
+            raise NotImplementedError("MultiheadAttention: key_padding_mask is not built")
+        if self.dropout > 0.0 and self.training:
+            raise NotImplementedError("MultiheadAttention: attention dropout is not built (DINO builds its layers with 0.0)")
+        E, W, b = self.embed_dim, self.in_proj_weight, self.in_proj_bias
+        mask = _byte_mask(attn_mask, query.shape[0], key.shape[0], query.device)
+        scale = HEAD_DIM ** -0.5
+        if query is key:
+            qk = F.linear(query, W[:2 * E], None if b is None else b[:2 * E])
+            v = F.linear(value, W[2 * E:], None if b is None else b[2 * E:])
+            _check(qk[..., :E], qk[..., E:], v, self.num_heads)
+            out = MaskedAttentionFunction.apply(qk, v, None, mask, self.num_heads, scale, True)
+        else:
+            q = F.linear(query, W[:E], None if b is None else b[:E])
+            k = F.linear(key, W[E:2 * E], None if b is None else b[E:2 * E])
+            v = F.linear(value, W[2 * E:], None if b is None else b[2 * E:])
+            _check(q, k, v, self.num_heads)
+            out = MaskedAttentionFunction.apply(q, k, v, mask, self.num_heads, scale, False)
+        return self.out_proj(out), None
+
+
+def _why_not(mha):
+    """Why a ``nn.MultiheadAttention`` cannot be replaced by the mirror, or ``None``."""
+    if not getattr(mha, "_qkv_same_embed_dim", True) or mha.in_proj_weight is None:
+        return "kdim / vdim other than embed_dim"
+    if mha.bias_k is not None or mha.bias_v is not None or mha.add_zero_attn:
+        return "bias_k / bias_v / add_zero_attn"
+    if getattr(mha, "batch_first", False):
+        return "batch_first"
+    if mha.embed_dim != mha.num_heads * HEAD_DIM:
+        return f"head dimension {mha.embed_dim / mha.num_heads:g}"
+    if mha.dropout > 0.0:
+        return "attention dropout"
+    return None
+
+
+def convert_self_attention(module):
+    """Replace, in place, every ``nn.MultiheadAttention`` below ``module`` that qualifies (embed_dim = 32 * heads, no dropout,
+    seq-first, no bias_k / add_zero_attn) with ``MultiheadAttention.adopt`` of it: the same ``Parameter`` objects, so optimizer
+    state, EMA pairs and ``state_dict`` keys are untouched.  Returns the number converted."""
+    done = 0
+    for parent in list(module.modules()):
+        for name, child in list(parent.named_children()):
+            if type(child) is nn.MultiheadAttention and _why_not(child) is None:
+                setattr(parent, name, MultiheadAttention.adopt(child))
+                done += 1
+    return done
