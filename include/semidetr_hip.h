@@ -775,6 +775,56 @@ int semidetr_self_attn_forward_f32(void *stream, const semidetr_self_attn *param
 int semidetr_self_attn_backward_f32(void *stream, const semidetr_self_attn *params /* host */, void *workspace,
                                     size_t workspace_bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * Residual add + LayerNorm + positional add (ABI 7, additive): the epilogue of a transformer sub-block and the with_pos_embed
+ * that opens the next one, row width 256.
+ *
+ * Replaces  `x = x + dropout(branch); x = norm(x)` and the following `with_pos_embed(x, pos)`
+ *           detr_od/models/utils/transformer.py:628-629, 636-637, 789-790, 811-812, 838-839 (and 624, 785)
+ *
+ *   s = x + residual;  mean = mean(s);  var = mean((s - mean)^2)  (biased, two passes over registers);
+ *   rstd = 1 / sqrt(var + eps);  y = (s - mean) * rstd * weight + bias;  q = y + pos.
+ *
+ * fp32 in / arithmetic / out, on `stream`, no host synchronisation, no memset, no float atomics; bitwise reproducible: the grid,
+ * the row -> wave map and the order of every sum depend on rows = rows0 * rows1 alone.  The parameter block is read on the host
+ * during the call.  x, residual, pos, gy and gq are (rows0, rows1, dim) tensors read through the strides of their two leading
+ * dimensions in ELEMENTS; the last dimension has stride 1 and every row starts 16-byte aligned (base aligned, strides
+ * non-negative multiples of 4), so transposed views and slices are read in place.  y, q and grad_x are contiguous
+ * (rows0, rows1, dim), mean and rstd contiguous (rows0 * rows1); weight, bias, y, q and grad_x are 16-byte aligned.
+ * dim != 256 is SEMIDETR_E_BADARG.
+ *
+ * semidetr_add_norm_forward_f32  -- one launch.  residual may be NULL (s = x).  pos and q are both NULL or both set.  Writes y,
+ *   q, mean, rstd.  Uses no workspace (NULL, 0 is accepted).
+ * semidetr_add_norm_backward_f32 -- two launches (one where grad_weight and grad_bias are both NULL).  gy and gq are the
+ *   upstream gradients of y and q; either may be NULL, not both.  With g = gy + gq and xhat = (x + residual - mean) * rstd
+ *   recomputed from the forward's inputs, mean and rstd:
+ *     grad_x = rstd * (g * weight - mean(g * weight) - xhat * mean(g * weight * xhat))   every element written once; it is the
+ *              gradient of x AND of residual, and gq is the gradient of pos;
+ *     grad_weight = sum_rows g * xhat,  grad_bias = sum_rows g   (each may be NULL): fp32 per lane over the 16 consecutive rows
+ *              of a wave in row order, the 4 waves of a workgroup in wave order into one slot of the workspace per 64 rows, the
+ *              slots in 16 contiguous chunks in index order in fp64, the chunks in order, one rounding.
+ *   bias, y, q and pos are not read.
+ * workspace: semidetr_add_norm_workspace_bytes(rows0 * rows1) bytes, 16-byte aligned, no initialisation needed (0 for rows
+ *   outside the limits); needed only where grad_weight or grad_bias is asked for.
+ * Limits: 1 <= rows0 * rows1 < 2^31, dim == 256.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct semidetr_add_norm {
+    int rows0, rows1, dim;
+    float eps;
+    const float *x, *residual, *pos;                      /* residual, pos: NULL = absent */
+    const float *gy, *gq;                                 /* backward only */
+    int64_t x_stride[2], residual_stride[2], pos_stride[2], gy_stride[2], gq_stride[2];   /* in elements */
+    const float *weight, *bias;                           /* (dim) */
+    float *y, *q;                                         /* forward: written */
+    float *mean, *rstd;                                   /* forward: written; backward: read */
+    float *grad_x, *grad_weight, *grad_bias;              /* backward: written */
+} semidetr_add_norm;
+size_t semidetr_add_norm_workspace_bytes(int64_t rows);
+int semidetr_add_norm_forward_f32(void *stream, const semidetr_add_norm *params /* host */, void *workspace,
+                                  size_t workspace_bytes);
+int semidetr_add_norm_backward_f32(void *stream, const semidetr_add_norm *params /* host */, void *workspace,
+                                   size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,10 @@ SIGNATURES = {
     "semidetr_self_attn_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
     "semidetr_self_attn_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
     "semidetr_self_attn_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
+    # residual add + LayerNorm + positional add (add_norm.py); the parameter block (semidetr_add_norm, add_norm._Params) is a host pointer
+    "semidetr_add_norm_workspace_bytes": (ctypes.c_size_t, [c_int64]),
+    "semidetr_add_norm_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
+    "semidetr_add_norm_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so

@@ -133,3 +133,35 @@ def bind_decoder_self_attention():
         wrapped._semidetr_self_attn = True
         cls.__init__ = wrapped
     return names, []
+
+
+def bind_layer_epilogues():
+    """Where ``detr_od`` is importable, rebind the transformer layers to the fused residual add + LayerNorm + positional add of
+    ``semi_detr_amd.add_norm``: ``DINOTransformerEncoderLayer.forward_ffn`` / ``.forward``, ``DINOTransformerEncoder.forward``
+    (which threads ``output + pos`` from layer to layer) and ``DINOTransformerDecoderLayer.forward_ffn`` / ``.forward_sa`` /
+    ``.forward_ca`` / ``.forward`` (``DeformableTransformer*Layer`` in trees that keep DINO's own layer names).  The layers' ``nn.LayerNorm``
+    modules stay where they are: the epilogue reads their ``weight``, ``bias`` and ``eps``.  Idempotent.  Returns
+    (bound, skipped) names."""
+    import importlib
+
+    from . import add_norm
+    table = ((("DINOTransformerEncoderLayer", "DeformableTransformerEncoderLayer"),
+              (("forward_ffn", add_norm.encoder_layer_forward_ffn), ("forward", add_norm.encoder_layer_forward))),
+             (("DINOTransformerEncoder",), (("forward", add_norm.encoder_forward),)),
+             (("DINOTransformerDecoderLayer", "DeformableTransformerDecoderLayer"),
+              (("forward_ffn", add_norm.decoder_layer_forward_ffn), ("forward_sa", add_norm.decoder_layer_forward_sa),
+               ("forward_ca", add_norm.decoder_layer_forward_ca), ("forward", add_norm.decoder_layer_forward))))
+    try:
+        m = importlib.import_module("detr_od.models.utils.transformer")
+    except ImportError:
+        m = None
+    done, skipped = [], []
+    for classes, methods in table:
+        cls = next((getattr(m, n) for n in classes if hasattr(m, n)), None) if m is not None else None
+        for name, fn in methods:
+            if cls is None:
+                skipped.append(f"{classes[0]}.{name}")
+            else:
+                setattr(cls, name, fn)              # a plain function: binds as a method, the layer is its first argument
+                done.append(f"{cls.__name__}.{name}")
+    return done, skipped
