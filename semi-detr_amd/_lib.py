@@ -17,21 +17,100 @@ EXPERIMENTS = os.environ.get("SEMIDETR_EXPERIMENTS", "0") not in ("", "0")
 LIB_PATH = os.path.join(_HERE, "csrc", "libsemidetr_hip_exp.so" if EXPERIMENTS else "libsemidetr_hip.so")
 
 c_void_p, c_int, c_int64, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
+c_float, c_size_t, POINTER = ctypes.c_float, ctypes.c_size_t, ctypes.POINTER
+
+# ---------------------------------------------------------------------------------------------
+# the ctypes mirrors of include/semidetr_hip.h: constants, parameter blocks, signatures.  A new op declares all three HERE;
+# tests/test_cabi_mirror.py compiles the header and checks every value, size, offset, field type and argument type below.
+# ---------------------------------------------------------------------------------------------
+# macro -> value: every macro a mirror depends on
+CONSTANTS = {
+    "SEMIDETR_ABI_VERSION": 7,
+    "SEMIDETR_EMA_CHUNK": 8192,
+    "SEMIDETR_GMM_COVARIANCE_DIAG": 1,
+    "SEMIDETR_SET_LOSS_MATCHED": 0, "SEMIDETR_SET_LOSS_DN": 1, "SEMIDETR_SET_LOSS_WARMUP": 2,
+    "SEMIDETR_SET_LOSS_MAX_LAYERS": 64, "SEMIDETR_SET_LOSS_NUM_STATS": 10, "SEMIDETR_SET_LOSS_NUM_TERMS": 5,
+    "SEMIDETR_DN_MAX_IMAGES": 64, "SEMIDETR_DN_NOISE_COLS": 10,
+    "SEMIDETR_QSEL_MAX_LEVELS": 8, "SEMIDETR_QSEL_MAX_K": 4096,
+    "SEMIDETR_DET_MAX_K": 2048,
+    "SEMIDETR_CONSIS_MAX_LAYERS": 16,
+}
+_DN_IMAGES, _CONSIS_LAYERS = CONSTANTS["SEMIDETR_DN_MAX_IMAGES"], CONSTANTS["SEMIDETR_CONSIS_MAX_LAYERS"]
+_STRIDE2 = c_int64 * 2                # the strides of a tensor's two leading dimensions, in elements
+
+
+def _f(ctype, names):
+    """The fields of one declaration of the header: ``int a, b;`` is ``_f(c_int, "a b")`` (every pointer is a ``c_void_p``)."""
+    return [(n, ctype) for n in names.split()]
 
 
 class CostParams(ctypes.Structure):
-    """Mirror of ``semidetr_cost_params`` (include/semidetr_hip.h)."""
-    _fields_ = [("cls_weight", ctypes.c_float), ("alpha", ctypes.c_float), ("gamma", ctypes.c_float),
-                ("eps", ctypes.c_float), ("reg_weight", ctypes.c_float), ("reg_xywh", ctypes.c_int),
-                ("iou_weight", ctypes.c_float), ("iou_giou", ctypes.c_int), ("pred_xyxy", ctypes.c_int)]
+    _fields_ = (_f(c_float, "cls_weight alpha gamma eps reg_weight") + _f(c_int, "reg_xywh") + _f(c_float, "iou_weight")
+                + _f(c_int, "iou_giou pred_xyxy"))
 
+
+class SetLossSegment(ctypes.Structure):
+    _fields_ = (_f(c_int, "kind num_layers num_images num_query num_classes")
+                + _f(c_void_p, "logits") + _f(c_int64 * 3, "logit_stride") + _f(c_void_p, "boxes") + _f(c_int64 * 3, "box_stride")
+                + _f(c_void_p, "labels label_weights bbox_targets bbox_weights metrics gt_offsets gt_boxes gt_labels")
+                + _f(c_int, "single_pad dn_groups") + _f(c_void_p, "img_wh")
+                + _f(c_float, "alpha gamma cls_weight l1_weight iou_weight iou_eps bg_cls_weight") + _f(c_int, "sync_cls")
+                + _f(c_void_p, "grad_logits grad_boxes"))
+
+
+class DnLayout(ctypes.Structure):
+    _fields_ = _f(c_int, "num_images single_pad groups") + _f(ctypes.c_int32 * (_DN_IMAGES + 1), "offsets")
+
+
+class DnBuild(ctypes.Structure):
+    _fields_ = (_f(DnLayout, "dn cons") + _f(ctypes.c_int32 * _DN_IMAGES, "src_counts") + _f(c_void_p * _DN_IMAGES, "labels boxes")
+                + _f(c_int, "box_stride num_known") + _f(c_void_p, "label_weight")
+                + _f(c_int, "num_embeddings hidden_dim num_classes num_queries") + _f(c_void_p, "noise image_noise")
+                + _f(c_float, "label_noise_threshold box_noise_scale")
+                + _f(c_void_p, "query_label query_bbox known_bid map_known_indice noised_labels pad_mask cons_rows cons_label "
+                               "attn_mask"))
+
+
+class DnConsistency(ctypes.Structure):
+    _fields_ = (_f(DnLayout, "cons") + _f(ctypes.c_int32 * _DN_IMAGES, "src_counts")
+                + _f(c_void_p * _DN_IMAGES, "pseudo_boxes det_boxes") + _f(c_int, "pseudo_stride det_stride num_known")
+                + _f(c_float * 2 * _DN_IMAGES, "tgt_wh src_wh")
+                + _f(c_void_p, "query_bbox known_bid map_known_indice loss_weights rois") + _f(c_float, "loss_weight"))
+
+
+class ConsisLayer(ctypes.Structure):
+    _fields_ = _f(c_void_p, "v1 v2") + _f(_STRIDE2, "v1_stride v2_stride") + _f(c_void_p, "grad_v1")
+
+
+class ConsisLoss(ctypes.Structure):
+    _fields_ = (_f(c_int, "num_layers batch num_query dim pad_size num_known bid_is_int64") + _f(c_float, "scale eps")
+                + _f(c_void_p, "known_bid map_known_indice loss_weights") + _f(ConsisLayer * _CONSIS_LAYERS, "layer"))
+
+
+class SelfAttn(ctypes.Structure):
+    _fields_ = (_f(c_int, "batch heads head_dim len_q len_k") + _f(c_float, "scale") + _f(c_void_p, "q k v")
+                + _f(_STRIDE2, "q_stride k_stride v_stride") + _f(c_void_p, "mask out lse grad_out grad_q grad_k grad_v")
+                + _f(_STRIDE2, "gq_stride gk_stride gv_stride"))
+
+
+class AddNorm(ctypes.Structure):
+    _fields_ = (_f(c_int, "rows0 rows1 dim") + _f(c_float, "eps") + _f(c_void_p, "x residual pos gy gq")
+                + _f(_STRIDE2, "x_stride residual_stride pos_stride gy_stride gq_stride")
+                + _f(c_void_p, "weight bias y q mean rstd grad_x grad_weight grad_bias"))
+
+
+# C struct -> mirror, in the header's order
+STRUCTS = {"semidetr_cost_params": CostParams, "semidetr_set_loss_segment": SetLossSegment, "semidetr_dn_layout": DnLayout,
+           "semidetr_dn_build": DnBuild, "semidetr_dn_consistency": DnConsistency, "semidetr_consis_layer": ConsisLayer,
+           "semidetr_consis_loss": ConsisLoss, "semidetr_self_attn": SelfAttn, "semidetr_add_norm": AddNorm}
+_SEGS, _WORK = POINTER(SetLossSegment), [c_void_p, c_size_t]        # a segment table; the (workspace, workspace_bytes) pair
 
 _MSDA_FWD = [c_void_p] * 6 + [c_int] * 7 + [c_void_p]
 _MSDA_BWD = [c_void_p] * 7 + [c_int] * 7 + [c_void_p] * 3
 _MSDA_FWD_F32 = [c_void_p] * 6 + [c_int] * 8 + [c_void_p]           # f32 entry points carry `flags`
 _MSDA_BWD_F32 = [c_void_p] * 7 + [c_int] * 8 + [c_void_p] * 3
 
-# name -> (restype, argtypes); must list every function include/semidetr_hip.h declares
+# name -> (restype, argtypes) of every function include/semidetr_hip.h declares
 SIGNATURES = {
     "semidetr_abi_version": (c_int, []),
     "semidetr_last_error": (ctypes.c_char_p, []),
@@ -44,63 +123,63 @@ SIGNATURES = {
     "semidetr_msda_mask_extents": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
     "semidetr_msda_last_kernels": (ctypes.c_char_p, []),
     "semidetr_msda_forward_h16": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
-    "semidetr_msda_backward_h16_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
+    "semidetr_msda_backward_h16_workspace_bytes": (c_size_t, [c_int] * 4),
     "semidetr_msda_backward_h16": (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 4),
     "semidetr_msda_h16_last_kernels": (ctypes.c_char_p, []),
     "semidetr_msda_set_forward_policy": (c_int, [c_int]),
     "semidetr_msda_forward_policy_state": (c_int, [c_void_p] * 4),
     "semidetr_msda_forward_policy_state_slot": (c_int, [c_int] + [c_void_p] * 4),
     "semidetr_msda_gather_choice": (c_int, [c_int]),
-    "semidetr_match_cost_f32": (c_int, [c_void_p] * 7 + [c_int] * 4 + [ctypes.POINTER(CostParams), c_void_p]),
+    "semidetr_match_cost_f32": (c_int, [c_void_p] * 7 + [c_int] * 4 + [POINTER(CostParams), c_void_p]),
     "semidetr_lsap_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "semidetr_lsap_solve": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6),
     "semidetr_build_targets": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int64] + [c_void_p] * 5),
     "semidetr_ema_multi_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_double]),
     "semidetr_ema_flat_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double]),
     "semidetr_pseudo_label_filter_f32": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 6),
-    "semidetr_nms_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
-    "semidetr_pseudo_nms_f32": (c_int, [c_void_p] * 4 + [c_int] * 3 + [ctypes.c_float, ctypes.c_float, c_int, c_void_p,
-                                                                       ctypes.c_size_t] + [c_void_p] * 3),
-    "semidetr_o2m_assign_f32": (c_int, [c_void_p] * 7 + [c_int] * 7 + [ctypes.c_float, ctypes.c_float] + [c_void_p] * 7),
-    "semidetr_tal_loss_workspace_bytes": (ctypes.c_size_t, []),
-    "semidetr_tal_loss_f32": (c_int, [c_void_p] * 4 + [c_int64, c_int, ctypes.c_float, c_int] + [c_void_p] * 3),
+    "semidetr_nms_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "semidetr_pseudo_nms_f32": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_float, c_float, c_int, c_void_p,
+                                                                       c_size_t] + [c_void_p] * 3),
+    "semidetr_o2m_assign_f32": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_float, c_float] + [c_void_p] * 7),
+    "semidetr_tal_loss_workspace_bytes": (c_size_t, []),
+    "semidetr_tal_loss_f32": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_float, c_int] + [c_void_p] * 3),
     "semidetr_transform_bboxes_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3),
     "semidetr_gmm_match_costs_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 2),
     "semidetr_gmm_fit_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 3 + [c_double, c_double, c_int]
                              + [c_void_p] * 4),
-    "semidetr_gmm_double_filter_f32": (c_int, [c_void_p] * 12 + [c_int, c_int, ctypes.c_float, c_int] + [c_void_p] * 10),
-    # the segment table (semidetr_set_loss_segment[], set_loss._Segment) is passed as a host pointer
-    "semidetr_set_loss_workspace_bytes": (c_int64, [c_void_p, c_int]),
-    "semidetr_set_loss_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64] + [c_void_p] * 4),
-    "semidetr_set_loss_finalize_f32": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 5),
-    "semidetr_set_loss_backward_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    # the parameter blocks (semidetr_dn_build / _consistency / _layout, dn_query._Build ...) are passed as host pointers
-    "semidetr_dn_build_f32": (c_int, [c_void_p, c_void_p]),
-    "semidetr_dn_consistency_f32": (c_int, [c_void_p, c_void_p]),
+    "semidetr_gmm_double_filter_f32": (c_int, [c_void_p] * 12 + [c_int, c_int, c_float, c_int] + [c_void_p] * 10),
+    # set_loss.py; the segment table is a host array
+    "semidetr_set_loss_workspace_bytes": (c_int64, [_SEGS, c_int]),
+    "semidetr_set_loss_forward_f32": (c_int, [c_void_p, _SEGS, c_int, c_void_p, c_int64] + [c_void_p] * 4),
+    "semidetr_set_loss_finalize_f32": (c_int, [c_void_p, _SEGS, c_int] + [c_void_p] * 5),
+    "semidetr_set_loss_backward_f32": (c_int, [c_void_p, _SEGS, c_int, c_void_p, c_void_p]),
+    # dn_query.py; here and below a parameter block is a host pointer, typed: the block of another op is an ArgumentError
+    "semidetr_dn_build_f32": (c_int, [c_void_p, POINTER(DnBuild)]),
+    "semidetr_dn_consistency_f32": (c_int, [c_void_p, POINTER(DnConsistency)]),
     "semidetr_dn_label_backward_f32": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
-    "semidetr_dn_gather_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "semidetr_dn_gather_rows_f32": (c_int, [c_void_p, POINTER(DnLayout), c_void_p, c_int, c_void_p]),
     # two-stage query selection (query_select.py)
     "semidetr_qsel_proposals_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 3),
     "semidetr_qsel_proposals_backward_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
-    "semidetr_qsel_topk_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),
-    "semidetr_qsel_topk_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
+    "semidetr_qsel_topk_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "semidetr_qsel_topk_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_size_t, c_void_p, c_void_p]),
     "semidetr_qsel_gather_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 4),
     "semidetr_qsel_gather_backward_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 2),
     # detection decode at evaluation / inference time (detect.py)
-    "semidetr_det_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
-    "semidetr_det_decode_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p, ctypes.c_size_t] + [c_void_p] * 4),
-    # cross-view consistency loss (consis_loss.py); the parameter block (semidetr_consis_loss, consis_loss._Params) is a host pointer
-    "semidetr_consis_loss_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
-    "semidetr_consis_loss_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
-    "semidetr_consis_loss_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
-    # decoder self-attention core (self_attn.py); the parameter block (semidetr_self_attn, self_attn._Params) is a host pointer
-    "semidetr_self_attn_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
-    "semidetr_self_attn_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
-    "semidetr_self_attn_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
-    # residual add + LayerNorm + positional add (add_norm.py); the parameter block (semidetr_add_norm, add_norm._Params) is a host pointer
-    "semidetr_add_norm_workspace_bytes": (ctypes.c_size_t, [c_int64]),
-    "semidetr_add_norm_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
-    "semidetr_add_norm_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
+    "semidetr_det_workspace_bytes": (c_size_t, [c_int] * 4),
+    "semidetr_det_decode_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p, c_size_t] + [c_void_p] * 4),
+    # cross-view consistency loss (consis_loss.py)
+    "semidetr_consis_loss_workspace_bytes": (c_size_t, [c_int] * 4),
+    "semidetr_consis_loss_forward_f32": (c_int, [c_void_p, POINTER(ConsisLoss)] + _WORK + [c_void_p]),
+    "semidetr_consis_loss_backward_f32": (c_int, [c_void_p, POINTER(ConsisLoss)] + _WORK + [c_void_p]),
+    # decoder self-attention core (self_attn.py)
+    "semidetr_self_attn_workspace_bytes": (c_size_t, [c_int] * 4),
+    "semidetr_self_attn_forward_f32": (c_int, [c_void_p, POINTER(SelfAttn)] + _WORK),
+    "semidetr_self_attn_backward_f32": (c_int, [c_void_p, POINTER(SelfAttn)] + _WORK),
+    # residual add + LayerNorm + positional add (add_norm.py)
+    "semidetr_add_norm_workspace_bytes": (c_size_t, [c_int64]),
+    "semidetr_add_norm_forward_f32": (c_int, [c_void_p, POINTER(AddNorm)] + _WORK),
+    "semidetr_add_norm_backward_f32": (c_int, [c_void_p, POINTER(AddNorm)] + _WORK),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so
@@ -214,6 +293,32 @@ def offsets(counts, dev):
     return offs, small_to_device(offs, torch.int32, dev)
 
 
+def rows_f32(t):
+    """A 3-D tensor as the kernels read it through a base pointer and the strides of its two leading dimensions: detached, fp32,
+    last stride 1, base and both leading strides 16-byte aligned; copied only where it is not."""
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(2) != 1 or t.data_ptr() % 16 or t.stride(0) % 4 or t.stride(1) % 4:
+        t = t.contiguous()
+    return t
+
+
+def set_rows(block, name, t, stride=None):
+    """``block.<name>`` = the data pointer of ``t`` and ``block.<stride>[0:2]`` = its two leading strides; the stride field is
+    ``<name>_stride`` unless named.  ``None`` leaves the field NULL."""
+    if t is None:
+        return
+    setattr(block, name, t.data_ptr())
+    st, strides = getattr(block, stride or name + "_stride"), t.stride()
+    st[0], st[1] = strides[0], strides[1]
+
+
+def cast(t, dtype):
+    """``t`` in ``dtype``, converted only where it is not; ``None`` stays ``None``."""
+    return t if t is None or t.dtype == dtype else t.to(dtype)
+
+
 FORWARD_POLICIES = {"adaptive": 0, "patch": 1, "window": 2}
 
 
@@ -226,7 +331,7 @@ def set_forward_policy(policy):
 def forward_policy_state(slot=0):
     """{'policy', 'mode' (0 patch / 1 window), 'far_fraction' (-1: no count received yet), 'updates'} of the current device and
     call-site slot (0 = the slot of callers that name none; MSDeformAttn instances hold theirs in ``policy_slot``)."""
-    pol, mode, upd, frac = c_int(), c_int(), ctypes.c_uint(), ctypes.c_float()
+    pol, mode, upd, frac = c_int(), c_int(), ctypes.c_uint(), c_float()
     check(lib().semidetr_msda_forward_policy_state_slot(int(slot), ctypes.byref(pol), ctypes.byref(mode), ctypes.byref(frac),
                                                         ctypes.byref(upd)), "semidetr_msda_forward_policy_state_slot")
     return {"policy": pol.value, "mode": mode.value, "far_fraction": frac.value, "updates": upd.value}

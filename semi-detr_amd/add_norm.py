@@ -27,35 +27,18 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 
 DIM = 256
+_Params = _lib.AddNorm
 
 
-class _Params(ctypes.Structure):
-    """Mirror of ``semidetr_add_norm`` (include/semidetr_hip.h)."""
-    _fields_ = [("rows0", ctypes.c_int), ("rows1", ctypes.c_int), ("dim", ctypes.c_int), ("eps", ctypes.c_float),
-                ("x", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("pos", ctypes.c_void_p),
-                ("gy", ctypes.c_void_p), ("gq", ctypes.c_void_p),
-                ("x_stride", ctypes.c_int64 * 2), ("residual_stride", ctypes.c_int64 * 2), ("pos_stride", ctypes.c_int64 * 2),
-                ("gy_stride", ctypes.c_int64 * 2), ("gq_stride", ctypes.c_int64 * 2),
-                ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("y", ctypes.c_void_p), ("q", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("rstd", ctypes.c_void_p),
-                ("grad_x", ctypes.c_void_p), ("grad_weight", ctypes.c_void_p), ("grad_bias", ctypes.c_void_p)]
-
-
-def _rows(t):
-    """A ``(..., 256)`` tensor as the kernel reads it: fp32 ``(rows0, rows1, 256)``, last stride 1, every row 16-byte aligned and
-    the two leading strides non-negative; copied only where not."""
+def _rows3(t):
+    """A ``(..., 256)`` tensor as ``(rows0, rows1, 256)`` for the kernel (``_lib.rows_f32``); ``None`` stays ``None``."""
     if t is None:
         return None
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
     if t.dim() == 2:
         t = t.unsqueeze(0)
     elif t.dim() != 3:
         t = t.reshape(1, -1, t.shape[-1])
-    if t.stride(2) != 1 or t.data_ptr() % 16 or t.stride(0) % 4 or t.stride(1) % 4 or t.stride(0) < 0 or t.stride(1) < 0:
-        t = t.contiguous()
-    return t
+    return _lib.rows_f32(t)
 
 
 def _vector(t):
@@ -63,14 +46,6 @@ def _vector(t):
     if t.dtype != torch.float32:
         t = t.float()
     return t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
-
-
-def _set(p, name, t):
-    if t is None:
-        return
-    setattr(p, name, t.data_ptr())
-    st = getattr(p, name + "_stride")
-    st[0], st[1] = t.stride(0), t.stride(1)
 
 
 def _check(x, residual, weight, bias, pos):
@@ -104,11 +79,11 @@ def _forward(x, residual, weight, bias, eps, pos):
     rstd = torch.empty((rows,), dtype=torch.float32, device=dev)
     if rows == 0:
         return y, q, mean, rstd
-    xr, rr, pr, w, b = _rows(x), _rows(residual), _rows(pos), _vector(weight), _vector(bias)
+    xr, rr, pr, w, b = _rows3(x), _rows3(residual), _rows3(pos), _vector(weight), _vector(bias)
     p = _Params()
     p.rows0, p.rows1, p.dim, p.eps = xr.shape[0], xr.shape[1], DIM, eps
     for name, t in (("x", xr), ("residual", rr), ("pos", pr)):
-        _set(p, name, t)
+        _lib.set_rows(p, name, t)
     p.weight, p.bias, p.y, p.mean, p.rstd = w.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr()
     if q is not None:
         p.q = q.data_ptr()
@@ -120,7 +95,7 @@ def add_layer_norm_backward(gy, gq, x, residual, weight, mean, rstd, need_weight
     """The backward launches alone: ``(dx, dweight, dbias)`` in fp32 from the upstream gradients of ``y`` and ``q`` (either may
     be ``None``) and what the forward saved; ``dweight`` / ``dbias`` are ``None`` where not needed."""
     dev = x.device
-    xr, rr, gyr, gqr, w = _rows(x), _rows(residual), _rows(gy), _rows(gq), _vector(weight)
+    xr, rr, gyr, gqr, w = _rows3(x), _rows3(residual), _rows3(gy), _rows3(gq), _vector(weight)
     rows = xr.shape[0] * xr.shape[1]
     dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
     dw = torch.empty((DIM,), dtype=torch.float32, device=dev) if need_weight else None
@@ -128,7 +103,7 @@ def add_layer_norm_backward(gy, gq, x, residual, weight, mean, rstd, need_weight
     p = _Params()
     p.rows0, p.rows1, p.dim, p.eps = xr.shape[0], xr.shape[1], DIM, 0.0
     for name, t in (("x", xr), ("residual", rr), ("gy", gyr), ("gq", gqr)):
-        _set(p, name, t)
+        _lib.set_rows(p, name, t)
     p.weight, p.mean, p.rstd, p.grad_x = w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr()
     work, nbytes = None, 0
     if need_weight or need_bias:
@@ -138,10 +113,6 @@ def add_layer_norm_backward(gy, gq, x, residual, weight, mean, rstd, need_weight
         work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     _lib.call("semidetr_add_norm_backward_f32", dev, ctypes.byref(p), work, nbytes)
     return dx, dw, db
-
-
-def _cast(t, dtype):
-    return t if t is None or t.dtype == dtype else t.to(dtype)
 
 
 class AddLayerNormFunction(torch.autograd.Function):
@@ -154,8 +125,8 @@ class AddLayerNormFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.dtypes = (x.dtype, None if residual is None else residual.dtype, weight.dtype, bias.dtype,
                       None if pos is None else pos.dtype)
-        y = _cast(y, x.dtype)
-        return y if pos is None else (y, _cast(q, x.dtype))
+        y = _lib.cast(y, x.dtype)
+        return y if pos is None else (y, _lib.cast(q, x.dtype))
 
     @staticmethod
     @once_differentiable
@@ -164,7 +135,7 @@ class AddLayerNormFunction(torch.autograd.Function):
         need, dt = ctx.needs_input_grad, ctx.dtypes
         if gy is None and gq is None:
             return (None,) * 6
-        gpos = _cast(gq, dt[4]) if need[5] and gq is not None else None
+        gpos = _lib.cast(gq, dt[4]) if need[5] and gq is not None else None
         if not any(need[:4]):
             return None, None, None, None, None, gpos
         if x.numel() == 0:                   # no rows, no launch: empty dx, zero sums
@@ -173,11 +144,11 @@ class AddLayerNormFunction(torch.autograd.Function):
             db = torch.zeros((DIM,), dtype=torch.float32, device=x.device) if need[3] else None
         else:
             dx, dw, db = add_layer_norm_backward(gy, gq, x, residual, weight, mean, rstd, need[2], need[3])
-        gx = _cast(dx, dt[0]) if need[0] else None
+        gx = _lib.cast(dx, dt[0]) if need[0] else None
         gres = None
         if residual is not None and need[1]:
-            gres = gx if gx is not None and dt[1] == dt[0] else _cast(dx, dt[1])
-        return gx, gres, _cast(dw, dt[2]), _cast(db, dt[3]), None, gpos
+            gres = gx if gx is not None and dt[1] == dt[0] else _lib.cast(dx, dt[1])
+        return gx, gres, _lib.cast(dw, dt[2]), _lib.cast(db, dt[3]), None, gpos
 
 
 def add_layer_norm(x, residual, weight, bias, eps=1e-5, pos=None):

@@ -33,21 +33,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 
-MAX_LAYERS = 16                          # SEMIDETR_CONSIS_MAX_LAYERS
-
-
-class _Layer(ctypes.Structure):
-    """Mirror of ``semidetr_consis_layer`` (include/semidetr_hip.h)."""
-    _fields_ = [("v1", ctypes.c_void_p), ("v2", ctypes.c_void_p), ("v1_stride", ctypes.c_int64 * 2),
-                ("v2_stride", ctypes.c_int64 * 2), ("grad_v1", ctypes.c_void_p)]
-
-
-class _Params(ctypes.Structure):
-    """Mirror of ``semidetr_consis_loss``."""
-    _fields_ = [("num_layers", ctypes.c_int), ("batch", ctypes.c_int), ("num_query", ctypes.c_int), ("dim", ctypes.c_int),
-                ("pad_size", ctypes.c_int), ("num_known", ctypes.c_int), ("bid_is_int64", ctypes.c_int),
-                ("scale", ctypes.c_float), ("eps", ctypes.c_float), ("known_bid", ctypes.c_void_p),
-                ("map_known_indice", ctypes.c_void_p), ("loss_weights", ctypes.c_void_p), ("layer", _Layer * MAX_LAYERS)]
+MAX_LAYERS = _lib.CONSTANTS["SEMIDETR_CONSIS_MAX_LAYERS"]
+_Layer, _Params = _lib.ConsisLayer, _lib.ConsisLoss
 
 
 def _require_cuda(t, what):
@@ -67,16 +54,6 @@ def _layers(hs, what):
     return hs
 
 
-def _rows(t):
-    """A layer as the kernel reads it: fp32, last stride 1, every row 16-byte aligned; copied only where it is not."""
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.stride(2) != 1 or t.data_ptr() % 16 or t.stride(0) % 4 or t.stride(1) % 4:
-        t = t.contiguous()
-    return t
-
-
 class ConsistencyLossFunction(torch.autograd.Function):
     """``apply(st, hs_v1)`` (stacked) or ``apply(st, *hs_v1)`` (list) -> the ``(L,)`` losses.  ``st``: the detached inputs and
     sizes (``consistency_loss`` builds it)."""
@@ -90,7 +67,7 @@ class ConsistencyLossFunction(torch.autograd.Function):
         ctx.dtypes = [t.dtype for t in hs1]
         if K == 0:
             return torch.full((L,), float("nan"), dtype=torch.float32, device=dev)
-        v1 = [_rows(t) for t in v1]
+        v1 = [_lib.rows_f32(t) for t in v1]
         p = _Params()
         p.num_layers, p.batch, p.num_query, p.dim, p.pad_size, p.num_known = L, B, Q, D, st["pad_size"], K
         p.scale, p.eps = st["scale"], st["eps"]
@@ -100,9 +77,8 @@ class ConsistencyLossFunction(torch.autograd.Function):
         p.loss_weights = w.data_ptr() if w is not None else None
         for l, (a, b) in enumerate(zip(v1, st["v2"])):
             ly = p.layer[l]
-            ly.v1, ly.v2 = a.data_ptr(), b.data_ptr()
-            ly.v1_stride[0], ly.v1_stride[1] = a.stride(0), a.stride(1)
-            ly.v2_stride[0], ly.v2_stride[1] = b.stride(0), b.stride(1)
+            _lib.set_rows(ly, "v1", a)
+            _lib.set_rows(ly, "v2", b)
         nbytes = _lib.lib().semidetr_consis_loss_workspace_bytes(L, K, B, st["pad_size"])
         work = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
         losses = torch.empty((L,), dtype=torch.float32, device=dev)
@@ -173,6 +149,6 @@ def consistency_loss(hs_v1, hs_v2, dn_meta, warm_up=True, scale=10.0, eps=1e-12)
             raise ValueError(f"consis_loss: {K} pairs but {weights.numel()} loss weights")
         weights = (weights if weights.dtype == torch.float32 else weights.float()).contiguous()
     st = dict(L=L, B=B, Q=Q, D=D, K=K, pad_size=pad_size, scale=float(scale), eps=float(eps), stacked=stacked,
-              bid=bid.contiguous(), idx=idx.contiguous(), weights=weights, v2=[_rows(t) for t in v2])
+              bid=bid.contiguous(), idx=idx.contiguous(), weights=weights, v2=[_lib.rows_f32(t) for t in v2])
     losses = ConsistencyLossFunction.apply(st, hs_v1) if stacked else ConsistencyLossFunction.apply(st, *v1)
     return {f"consis_loss.d{l}": v for l, v in enumerate(losses.unbind(0))}

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 
-MAX_K = 2048                               # SEMIDETR_DET_MAX_K
+MAX_K = _lib.CONSTANTS["SEMIDETR_DET_MAX_K"]
 
 
 def _last_layer(all_cls_scores, all_bbox_preds):

@@ -26,37 +26,9 @@ import torch
 
 from . import _lib
 
-MAX_IMAGES, NOISE_COLS = 64, 10          # SEMIDETR_DN_MAX_IMAGES, SEMIDETR_DN_NOISE_COLS
+MAX_IMAGES, NOISE_COLS = _lib.CONSTANTS["SEMIDETR_DN_MAX_IMAGES"], _lib.CONSTANTS["SEMIDETR_DN_NOISE_COLS"]
 CONSISTENCY_GROUPS = 5                   # dn_number_1, dino_detr_ssod.py:533
-
-
-class _Layout(ctypes.Structure):
-    """Mirror of ``semidetr_dn_layout`` (include/semidetr_hip.h)."""
-    _fields_ = [("num_images", ctypes.c_int), ("single_pad", ctypes.c_int), ("groups", ctypes.c_int),
-                ("offsets", ctypes.c_int32 * (MAX_IMAGES + 1))]
-
-
-class _Build(ctypes.Structure):
-    """Mirror of ``semidetr_dn_build``."""
-    _fields_ = [("dn", _Layout), ("cons", _Layout), ("src_counts", ctypes.c_int32 * MAX_IMAGES),
-                ("labels", ctypes.c_void_p * MAX_IMAGES), ("boxes", ctypes.c_void_p * MAX_IMAGES),
-                ("box_stride", ctypes.c_int), ("num_known", ctypes.c_int), ("label_weight", ctypes.c_void_p),
-                ("num_embeddings", ctypes.c_int), ("hidden_dim", ctypes.c_int), ("num_classes", ctypes.c_int),
-                ("num_queries", ctypes.c_int), ("noise", ctypes.c_void_p), ("image_noise", ctypes.c_void_p),
-                ("label_noise_threshold", ctypes.c_float), ("box_noise_scale", ctypes.c_float),
-                ("query_label", ctypes.c_void_p), ("query_bbox", ctypes.c_void_p), ("known_bid", ctypes.c_void_p),
-                ("map_known_indice", ctypes.c_void_p), ("noised_labels", ctypes.c_void_p), ("pad_mask", ctypes.c_void_p),
-                ("cons_rows", ctypes.c_void_p), ("cons_label", ctypes.c_void_p), ("attn_mask", ctypes.c_void_p)]
-
-
-class _Consistency(ctypes.Structure):
-    """Mirror of ``semidetr_dn_consistency``."""
-    _fields_ = [("cons", _Layout), ("src_counts", ctypes.c_int32 * MAX_IMAGES),
-                ("pseudo_boxes", ctypes.c_void_p * MAX_IMAGES), ("det_boxes", ctypes.c_void_p * MAX_IMAGES),
-                ("pseudo_stride", ctypes.c_int), ("det_stride", ctypes.c_int), ("num_known", ctypes.c_int),
-                ("tgt_wh", ctypes.c_float * 2 * MAX_IMAGES), ("src_wh", ctypes.c_float * 2 * MAX_IMAGES),
-                ("query_bbox", ctypes.c_void_p), ("known_bid", ctypes.c_void_p), ("map_known_indice", ctypes.c_void_p),
-                ("loss_weights", ctypes.c_void_p), ("rois", ctypes.c_void_p), ("loss_weight", ctypes.c_float)]
+_Layout, _Build, _Consistency = _lib.DnLayout, _lib.DnBuild, _lib.DnConsistency
 
 
 def make_layout(counts, single_pad, groups):
@@ -89,7 +61,7 @@ def _require_cuda(t, what):
         raise RuntimeError(f"dn_query: {what} must live on the GPU (no CPU fallback)")
 
 
-def _rows(t, dtype, dev):
+def _entry(t, dtype, dev):
     """A per-image list entry as a contiguous device tensor (a no-op for what the callers pass)."""
     t = t.detach()
     if t.device != dev or t.dtype != dtype:
@@ -212,7 +184,7 @@ def _cdn(labels_list, boxes_list, standin, dn_number, label_noise_ratio, box_noi
     for b, n in enumerate(src):
         p.src_counts[b] = n
         if n:
-            lab, box = _rows(labels_list[b], torch.int64, dev), _rows(boxes_list[b], torch.float32, dev)
+            lab, box = _entry(labels_list[b], torch.int64, dev), _entry(boxes_list[b], torch.float32, dev)
             if box.dim() != 2 or box.shape[1] != 4:
                 raise ValueError(f"dn_query: boxes must be (n, 4) normalised cxcywh, got {tuple(box.shape)}")
             keep += [lab, box]
@@ -281,13 +253,13 @@ def consistency_queries(pseudo_bboxes, det_bboxes, tgt_shapes, src_shapes, loss_
         h, w = src_shapes[b][0], src_shapes[b][1]
         p.src_wh[b][0], p.src_wh[b][1] = float(w), float(h)
         if n:
-            box = _rows(pseudo_bboxes[b], torch.float32, dev)
+            box = _entry(pseudo_bboxes[b], torch.float32, dev)
             if box.dim() != 2 or box.shape[1] != 4:
                 raise ValueError(f"dn_query: pseudo boxes must be (n, 4) xyxy, got {tuple(box.shape)}")
             keep.append(box)
             p.pseudo_boxes[b] = box.data_ptr()
             if with_rois:
-                det = _rows(det_bboxes[b], torch.float32, dev)
+                det = _entry(det_bboxes[b], torch.float32, dev)
                 keep.append(det)
                 p.det_boxes[b] = det.data_ptr()
     p.pseudo_stride, p.det_stride, p.num_known = 4, (det_stride.pop() if det_stride else 4), K1

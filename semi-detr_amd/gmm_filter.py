@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from .matcher import lsap_batch, match_cost_batch
 
-COVARIANCE_DIAG = 1                 # SEMIDETR_GMM_COVARIANCE_DIAG
+COVARIANCE_DIAG = _lib.CONSTANTS["SEMIDETR_GMM_COVARIANCE_DIAG"]
 
 
 def _check_covariance(covariance_type):

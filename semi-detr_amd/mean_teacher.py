@@ -22,7 +22,7 @@ except ImportError:  # mmcv is not installed in the build image
     def is_module_wrapper(module):
         return isinstance(module, (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel))
 
-EMA_CHUNK = 8192   # == SEMIDETR_EMA_CHUNK in include/semidetr_hip.h
+EMA_CHUNK = _lib.CONSTANTS["SEMIDETR_EMA_CHUNK"]
 
 
 def ema_momentum(momentum, warm_up, step):

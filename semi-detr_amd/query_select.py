@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 
-MAX_LEVELS, MAX_K = 8, 4096                # SEMIDETR_QSEL_MAX_LEVELS, SEMIDETR_QSEL_MAX_K
+MAX_LEVELS, MAX_K = _lib.CONSTANTS["SEMIDETR_QSEL_MAX_LEVELS"], _lib.CONSTANTS["SEMIDETR_QSEL_MAX_K"]
 
 
 def _require(t, what):

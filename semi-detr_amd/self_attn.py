@@ -26,27 +26,7 @@ from torch.nn import functional as F
 from . import _lib
 
 HEAD_DIM = 32
-
-
-class _Params(ctypes.Structure):
-    """Mirror of ``semidetr_self_attn`` (include/semidetr_hip.h)."""
-    _fields_ = [("batch", ctypes.c_int), ("heads", ctypes.c_int), ("head_dim", ctypes.c_int), ("len_q", ctypes.c_int),
-                ("len_k", ctypes.c_int), ("scale", ctypes.c_float),
-                ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p),
-                ("q_stride", ctypes.c_int64 * 2), ("k_stride", ctypes.c_int64 * 2), ("v_stride", ctypes.c_int64 * 2),
-                ("mask", ctypes.c_void_p), ("out", ctypes.c_void_p), ("lse", ctypes.c_void_p), ("grad_out", ctypes.c_void_p),
-                ("grad_q", ctypes.c_void_p), ("grad_k", ctypes.c_void_p), ("grad_v", ctypes.c_void_p),
-                ("gq_stride", ctypes.c_int64 * 2), ("gk_stride", ctypes.c_int64 * 2), ("gv_stride", ctypes.c_int64 * 2)]
-
-
-def _rows(t):
-    """A ``(L, B, E)`` tensor as the kernel reads it: fp32, last stride 1, every row 16-byte aligned; copied only where not."""
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.stride(2) != 1 or t.data_ptr() % 16 or t.stride(0) % 4 or t.stride(1) % 4:
-        t = t.contiguous()
-    return t
+_Params = _lib.SelfAttn
 
 
 def _split(x, y, z, packed_qk):
@@ -60,10 +40,9 @@ def _params(q, k, v, mask, heads, scale):
     p = _Params()
     (Lq, B, E), Lk = q.shape, k.shape[0]
     p.batch, p.heads, p.head_dim, p.len_q, p.len_k, p.scale = B, heads, E // heads, Lq, Lk, scale
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        setattr(p, name, t.data_ptr())
-        st = getattr(p, name + "_stride")
-        st[0], st[1] = t.stride(0), t.stride(1)
+    _lib.set_rows(p, "q", q)
+    _lib.set_rows(p, "k", k)
+    _lib.set_rows(p, "v", v)
     p.mask = mask.data_ptr() if mask is not None else None
     return p
 
@@ -81,7 +60,7 @@ class MaskedAttentionFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, z, mask, num_heads, scale, packed_qk):
-        q, k, v = (_rows(t) for t in _split(x, y, z, packed_qk))
+        q, k, v = (_lib.rows_f32(t) for t in _split(x, y, z, packed_qk))
         dev = q.device
         p = _params(q, k, v, mask, num_heads, scale)
         out = torch.empty(q.shape, dtype=torch.float32, device=dev)
@@ -92,8 +71,7 @@ class MaskedAttentionFunction(torch.autograd.Function):
         ctx.num_heads, ctx.scale, ctx.packed_qk = num_heads, scale, packed_qk
         ctx.dtypes = [t.dtype if t is not None else None for t in (x, y, z)]
         ctx.save_for_backward(x, y, z, mask, out, lse)
-        result = out if x.dtype == torch.float32 else out.to(x.dtype)
-        return result
+        return _lib.cast(out, x.dtype)
 
     @staticmethod
     @once_differentiable
@@ -102,7 +80,7 @@ class MaskedAttentionFunction(torch.autograd.Function):
         need = ctx.needs_input_grad[:3]
         if not any(need):
             return (None,) * 7
-        q, k, v = (_rows(t) for t in _split(x, y, z, ctx.packed_qk))
+        q, k, v = (_lib.rows_f32(t) for t in _split(x, y, z, ctx.packed_qk))
         dev = q.device
         g = g.detach()
         if g.dtype != torch.float32:
@@ -121,19 +99,14 @@ class MaskedAttentionFunction(torch.autograd.Function):
             gq = torch.empty(q.shape, dtype=torch.float32, device=dev) if need_q else None
             gk = torch.empty(k.shape, dtype=torch.float32, device=dev) if need_k else None
         gv = torch.empty(v.shape, dtype=torch.float32, device=dev) if need_v else None
-        for name, t in (("q", gq), ("k", gk), ("v", gv)):
-            if t is not None:
-                setattr(p, "grad_" + name, t.data_ptr())
-                st = getattr(p, "g" + name + "_stride")
-                st[0], st[1] = t.stride(0), t.stride(1)
+        _lib.set_rows(p, "grad_q", gq, "gq_stride")
+        _lib.set_rows(p, "grad_k", gk, "gk_stride")
+        _lib.set_rows(p, "grad_v", gv, "gv_stride")
         work, nbytes = _workspace(p, dev)
         _lib.call("semidetr_self_attn_backward_f32", dev, ctypes.byref(p), work, nbytes)
-
-        def cast(t, dt):
-            return t if t is None or t.dtype == dt else t.to(dt)
         if ctx.packed_qk:
-            return cast(gx, ctx.dtypes[0]), cast(gv, ctx.dtypes[1]), None, None, None, None, None
-        return cast(gq, ctx.dtypes[0]), cast(gk, ctx.dtypes[1]), cast(gv, ctx.dtypes[2]), None, None, None, None
+            return _lib.cast(gx, ctx.dtypes[0]), _lib.cast(gv, ctx.dtypes[1]), None, None, None, None, None
+        return _lib.cast(gq, ctx.dtypes[0]), _lib.cast(gk, ctx.dtypes[1]), _lib.cast(gv, ctx.dtypes[2]), None, None, None, None
 
 
 def _byte_mask(attn_mask, Lq, Lk, dev):

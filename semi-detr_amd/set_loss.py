@@ -12,8 +12,6 @@
   CUDA op ``sigmoid_focal_loss``.
 * ``set_losses`` is the lower level: a list of ``SetLossSegment`` -> one 0-d loss per (segment, layer, term).
 """
-import ctypes
-
 import torch
 import torch.distributed as dist
 from torch import nn
@@ -21,27 +19,14 @@ from torch import nn
 from . import _lib
 from .targets import _targets_stacked
 
-MATCHED, DN, WARMUP = 0, 1, 2             # SEMIDETR_SET_LOSS_*
-NUM_STATS, NUM_TERMS, MAX_LAYERS = 10, 5, 64
+MATCHED, DN, WARMUP, NUM_STATS, NUM_TERMS, MAX_LAYERS = (
+    _lib.CONSTANTS["SEMIDETR_SET_LOSS_" + n] for n in ("MATCHED", "DN", "WARMUP", "NUM_STATS", "NUM_TERMS", "MAX_LAYERS"))
 TERMS = ("loss_cls", "loss_bbox", "loss_iou", "loss_bbox_xy", "loss_bbox_hw")
 STATS = ("cls_sum", "l1_sum", "l1_xy", "l1_hw", "giou_sum", "num_pos", "num_bw_rows", "num_any_bw_rows", "pos_bw0_sum",
          "metric_sum")
 
 
-class _Segment(ctypes.Structure):
-    """Mirror of ``semidetr_set_loss_segment`` (include/semidetr_hip.h)."""
-    _fields_ = [("kind", ctypes.c_int), ("num_layers", ctypes.c_int), ("num_images", ctypes.c_int),
-                ("num_query", ctypes.c_int), ("num_classes", ctypes.c_int),
-                ("logits", ctypes.c_void_p), ("logit_stride", ctypes.c_int64 * 3),
-                ("boxes", ctypes.c_void_p), ("box_stride", ctypes.c_int64 * 3),
-                ("labels", ctypes.c_void_p), ("label_weights", ctypes.c_void_p), ("bbox_targets", ctypes.c_void_p),
-                ("bbox_weights", ctypes.c_void_p), ("metrics", ctypes.c_void_p),
-                ("gt_offsets", ctypes.c_void_p), ("gt_boxes", ctypes.c_void_p), ("gt_labels", ctypes.c_void_p),
-                ("single_pad", ctypes.c_int), ("dn_groups", ctypes.c_int), ("img_wh", ctypes.c_void_p),
-                ("alpha", ctypes.c_float), ("gamma", ctypes.c_float), ("cls_weight", ctypes.c_float),
-                ("l1_weight", ctypes.c_float), ("iou_weight", ctypes.c_float), ("iou_eps", ctypes.c_float),
-                ("bg_cls_weight", ctypes.c_float), ("sync_cls", ctypes.c_int),
-                ("grad_logits", ctypes.c_void_p), ("grad_boxes", ctypes.c_void_p)]
+_Segment = _lib.SetLossSegment
 
 
 def _ptr(t):

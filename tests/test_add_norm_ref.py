@@ -3,8 +3,6 @@
 not too tight; eight mutations of the formulas are rejected, so they are not too loose -- and the host surface of
 ``semi_detr_amd.add_norm`` that needs no GPU."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,8 +12,6 @@ from torch.nn import functional as F
 
 import add_norm_cases as C
 import add_norm_ref64 as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def torch_cpu(case):
@@ -105,22 +101,9 @@ SYMBOLS = ("semidetr_add_norm_workspace_bytes", "semidetr_add_norm_forward_f32",
 def test_library_exports_the_three_symbols_and_signatures_match_the_header():
     import semi_detr_amd
     lib = semi_detr_amd._lib.lib()
-    header = open(os.path.join(ROOT, "include", "semidetr_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    for n in SYMBOLS:
+    for n in SYMBOLS:                            # their types and the block's layout: tests/test_cabi_mirror.py
         assert hasattr(lib, n) and n in semi_detr_amd._lib.SIGNATURES
-        decl = re.search(r"(\w+)\s+%s\s*\(([^)]*)\)" % n, header)
-        assert decl, n
-        res, args = semi_detr_amd._lib.SIGNATURES[n]
-        assert len([a for a in decl.group(2).split(",") if a.strip()]) == len(args), n
-        assert {"size_t": ctypes.c_size_t, "int": ctypes.c_int}[decl.group(1)] is res
     assert lib.semidetr_abi_version() == 7
-    # the ctypes mirror of the parameter block has the header's fields in the header's order
-    from semi_detr_amd.add_norm import _Params
-    block = re.search(r"typedef struct semidetr_add_norm \{(.*?)\} semidetr_add_norm;", header, flags=re.S).group(1)
-    fields = [re.sub(r"[\s*]|\[2\]", "", f) for line in block.split(";") for f in re.sub(r"^\s*(const\s+)?\w+\s", "", line).split(",")
-              if f.strip()]
-    assert fields == [f[0] for f in _Params._fields_]
     assert lib.semidetr_add_norm_workspace_bytes(0) == 0 and lib.semidetr_add_norm_workspace_bytes(2 ** 31) == 0
     assert lib.semidetr_add_norm_workspace_bytes(64) == 2048 and lib.semidetr_add_norm_workspace_bytes(2051) == 33 * 2048
 

@@ -11,16 +11,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared_functions(header="semidetr_hip.h"):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(semidetr_[a-z0-9_]+)\s*\(", src)))
-
-
 def test_library_exports_every_declared_symbol():
     import ctypes
     import semi_detr_amd
-    names = _declared_functions()
+    from test_cabi_mirror import declarations
+    names = sorted(declarations())
     assert len(names) >= 12
     csrc = os.path.join(ROOT, "semi-detr_amd", "csrc")
     handle = ctypes.CDLL(os.path.join(csrc, "libsemidetr_hip.so"))
@@ -29,7 +24,7 @@ def test_library_exports_every_declared_symbol():
     assert sorted(semi_detr_amd._lib.SIGNATURES) == names
     assert semi_detr_amd._lib.lib().semidetr_abi_version() == 7
     # the tuning / measurement entry points live ONLY in the experiments build (not in what ships)
-    extra = _declared_functions("semidetr_hip_experiments.h")
+    extra = sorted(declarations("semidetr_hip_experiments.h"))
     assert extra == sorted(semi_detr_amd._lib.EXPERIMENT_SIGNATURES) and len(extra) == 3
     exp = ctypes.CDLL(os.path.join(csrc, "libsemidetr_hip_exp.so"))
     for n in names + extra:

@@ -6,10 +6,13 @@ is how the Python side reaches them: device guard, stream lookup, pointer conver
                                     [--out profiles/host_call_probe.txt]
     python tools/host_call_probe.py --tree DIR          (what the first form starts: one JSON line of us per call)
 
-Three launch-bound calls at toy sizes, so that the call overhead is what is timed:
+Launch-bound calls at toy sizes, so that the call overhead is what is timed:
     ema       ema_update_flat_ on 4096 elements
     lsap      lsap_batch on one 16 x 4 problem
     select    select_queries at N=1, S=1024, C=8, k=64, d_model=32
+    addnorm   add_layer_norm forward + backward on (2, 300, 256)
+    attn      masked_attention forward + backward at Lq = Lk = 64, B = 1, 8 heads
+    consis    consistency_loss forward + backward at L = 2, B = 1, Q = 32, K = 8, D = 256
 Wall time per call over at least 100 calls and at least 0.25 s after 20 warm-up calls, including the final synchronize.  Every
 measurement is a fresh child process that imports the package from its tree (each tree needs its built library); the trees
 alternate, ``--rounds`` times each, and the table gives min .. max per tree.  The branch passes where its minimum is no higher
@@ -25,7 +28,7 @@ import subprocess
 import sys
 import time
 
-CALLS = ("ema", "lsap", "select")
+CALLS = ("ema", "lsap", "select", "addnorm", "attn", "consis")
 
 
 def wall(fn, sync, calls=100, warmup=20, min_seconds=0.25):
@@ -63,9 +66,26 @@ def measure(tree):
     logits = torch.randn(N, S, C, device=dev, generator=g)
     coord, prop = torch.randn(N, S, 4, device=dev, generator=g), torch.randn(N, S, 4, device=dev, generator=g)
     memory = torch.randn(N, S, D, device=dev, generator=g)
+
+    def leaves(*shape, n=1):
+        return [torch.randn(*shape, device=dev, generator=g).requires_grad_(True) for _ in range(n)]
+
+    def train(forward, inputs, grads):           # forward + backward without accumulating into .grad
+        def run():
+            with torch.enable_grad():
+                torch.autograd.grad(forward(), inputs, grads)
+        return run
+    xr, wb, qkv = leaves(2, 300, 256, n=2), leaves(256, n=2), leaves(64, 1, 256, n=3)
+    hs1, hs2 = leaves(1, 32, 256, n=2), [t.detach() for t in leaves(1, 32, 256, n=2)]
+    meta = {"pad_size_1": 8, "known_bid_1": torch.zeros(8, device=dev), "map_known_indice_1": torch.arange(8, device=dev),
+            "loss_weights": torch.ones(8, 1, device=dev)}
+    one = torch.ones((), device=dev)
     fns = {"ema": lambda: s.ema_update_flat_(teacher, student, 0.999),
            "lsap": lambda: lsap_batch(cost, offs_dev, offs, Q),
-           "select": lambda: s.select_queries(logits, coord, prop, memory, k)}
+           "select": lambda: s.select_queries(logits, coord, prop, memory, k),
+           "addnorm": train(lambda: s.add_layer_norm(*xr, *wb), xr + wb, torch.ones(2, 300, 256, device=dev)),
+           "attn": train(lambda: s.masked_attention(*qkv, 8), qkv, torch.ones(64, 1, 256, device=dev)),
+           "consis": train(lambda: list(s.consistency_loss(hs1, hs2, meta).values()), hs1, [one, one])}
     with torch.no_grad():
         res = {name: wall(fns[name], torch.cuda.synchronize) for name in CALLS}
     res["device"] = torch.cuda.get_device_name(0)
