@@ -147,6 +147,44 @@ int semidetr_msda_fused_backward_f32(void *stream, const float *grad_out, const 
                                      int spatial_size, int num_heads, int channels, int num_levels,
                                      int num_query, int num_point, int flags, float *grad_value,
                                      float *grad_sampling_offsets, float *grad_attn_logits);
+/* ---------------------------------------------------------------------------------------------
+ * The f32 entry points with the level table on the host as well (ABI 7, additive).  `host_spatial_shapes`: a HOST copy of
+ * spatial_shapes (num_levels x {H, W}, int64) that the caller already holds, or NULL; everything else as in the call of the same name
+ * without `_v2`, which is this call with NULL.  The encoder kernels (SEMIDETR_MSDA_QUERIES_ARE_PIXELS) cut the finest level into regions,
+ * one workgroup per (image, region, head); with the table on the host the library picks the region grid per launch so that the
+ * workgroups fill whole waves of the device's compute units, and launches exactly batch x regions x num_heads of them (see
+ * semidetr_msda_set_region_grid below).  The device table stays what the kernels read: a host copy that disagrees with it costs speed,
+ * never correctness (a kernel takes no grid coarser than its windows allow, and walks whatever regions the grid size leaves over).
+ * Results are the same either way up to fp32 summation order.  NULL, more than 8 levels, or a level of more than 32766 rows or
+ * columns: the launch is exactly that of the call without `_v2`.
+ * ------------------------------------------------------------------------------------------- */
+int semidetr_msda_forward_f32_v2(void *stream, const float *value, const int64_t *spatial_shapes,
+                                 const int64_t *level_start, const float *sampling_loc,
+                                 const float *attn_weight, int batch, int spatial_size, int num_heads,
+                                 int channels, int num_levels, int num_query, int num_point, int flags, float *out,
+                                 const int64_t *host_spatial_shapes);
+int semidetr_msda_backward_f32_v2(void *stream, const float *grad_out, const float *value,
+                                  const int64_t *spatial_shapes, const int64_t *level_start,
+                                  const float *sampling_loc, const float *attn_weight, int batch,
+                                  int spatial_size, int num_heads, int channels, int num_levels,
+                                  int num_query, int num_point, int flags, float *grad_value,
+                                  float *grad_sampling_loc, float *grad_attn_weight, const int64_t *host_spatial_shapes);
+int semidetr_msda_fused_forward_f32_v2(void *stream, const float *value, const int64_t *spatial_shapes,
+                                       const int64_t *level_start, const float *reference_points, int ref_dim,
+                                       const float *sampling_offsets, const float *attn_logits,
+                                       const unsigned char *padding_mask, const int *mask_extents, int batch,
+                                       int spatial_size, int num_heads, int channels, int num_levels,
+                                       int num_query, int num_point, int flags, float *out,
+                                       const int64_t *host_spatial_shapes);
+int semidetr_msda_fused_backward_f32_v2(void *stream, const float *grad_out, const float *value,
+                                        const int64_t *spatial_shapes, const int64_t *level_start,
+                                        const float *reference_points, int ref_dim,
+                                        const float *sampling_offsets, const float *attn_logits,
+                                        const unsigned char *padding_mask, const int *mask_extents, int batch,
+                                        int spatial_size, int num_heads, int channels, int num_levels,
+                                        int num_query, int num_point, int flags, float *grad_value,
+                                        float *grad_sampling_offsets, float *grad_attn_logits,
+                                        const int64_t *host_spatial_shapes);
 /* Summarise a padding mask for the two calls above: one small launch (batch x num_levels workgroups, reads the mask once).
  *   extents (batch, num_levels) int32: vh | vw << 16 when level l of image n is padded exactly on rows >= vh and columns >= vw
  *   (no padding: H_l | W_l << 16; everything padded: 0), -1 otherwise (and for levels of more than 32767 rows / columns).  Valid for as long as the mask bytes and the
@@ -192,6 +230,28 @@ int semidetr_msda_forward_policy_state_slot(int slot, int *policy, int *mode, fl
 /* What an encoder backward of `slot` issued NOW would pick for its small-gradient half, as the flag to pass later:
  * SEMIDETR_MSDA_GATHER_WINDOW or SEMIDETR_MSDA_GATHER_PATCH (never 0, never an error: an unknown slot / device answers PATCH). */
 int semidetr_msda_gather_choice(int slot);
+
+/* ---------------------------------------------------------------------------------------------
+ * The REGION GRID of the three encoder window kernels (ABI 7, additive): SEMIDETR_MSDA_GRID_FORWARD the window forward (msda_rw_d32),
+ * _GATHER the window gather (msda_gw_d32), _SCATTER the region scatter of grad_value (msda_bwd_scatter_d32_reg).  Each cuts the finest
+ * level into nry x nrx regions; ceil(H / RTH) x ceil(W / RTW) -- RTH x RTW the largest region the kernel's windows are sized for -- is the
+ * coarsest grid, any finer one gives the same results.
+ * semidetr_msda_set_region_grid(kernel, nry, nrx): pin the grid of `kernel` (process-wide; tests, A/B timing); 0, 0: automatic (default).
+ *   A pinned count below the coarsest one is raised to it; one above the level's pixels is legal (regions without a level-0 pixel).
+ *   Counts up to 32767 each, 2^22 regions at most.
+ *   Automatic: with a host table (the `_v2` calls) the grid that minimises ceil(batch x regions x num_heads / slots) x (set-up +
+ *   rounds of the largest region), ties to the coarsest; without one the coarsest.
+ * semidetr_msda_region_grid_query: what a launch of `kernel` with this host table (or NULL), batch, num_heads on a device of num_cus
+ *   compute units takes, pins included; needs no device.  grid6 = {nry, nrx (0, 0: the kernel's own coarsest grid), regions (0: table
+ *   unknown -- the grid size is a hint), workgroups = batch x regions x num_heads, 1 if the forward adds its tail-split helpers (one
+ *   per compute unit), queries of the largest region}.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_MSDA_GRID_FORWARD 0
+#define SEMIDETR_MSDA_GRID_GATHER 1
+#define SEMIDETR_MSDA_GRID_SCATTER 2
+int semidetr_msda_set_region_grid(int kernel, int nry, int nrx);
+int semidetr_msda_region_grid_query(int kernel, const int64_t *host_spatial_shapes, int num_levels, int batch, int num_heads,
+                                    int num_cus, int *grid6);
 
 /* Names of the device kernels the LAST semidetr_msda_* call of the calling thread launched ("+"-separated, as the
  * profiler prints their base names), so that a benchmark reports what actually ran instead of a hand-kept table. */

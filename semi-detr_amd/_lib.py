@@ -120,6 +120,11 @@ SIGNATURES = {
     "semidetr_msda_backward_f64": (c_int, _MSDA_BWD),
     "semidetr_msda_fused_forward_f32": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 4 + [c_int] * 8 + [c_void_p]),
     "semidetr_msda_fused_backward_f32": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 4 + [c_int] * 8 + [c_void_p] * 3),
+    # ... with a host copy of spatial_shapes last (or None)
+    "semidetr_msda_forward_f32_v2": (c_int, _MSDA_FWD_F32 + [c_void_p]),
+    "semidetr_msda_backward_f32_v2": (c_int, _MSDA_BWD_F32 + [c_void_p]),
+    "semidetr_msda_fused_forward_f32_v2": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 4 + [c_int] * 8 + [c_void_p] * 2),
+    "semidetr_msda_fused_backward_f32_v2": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 4 + [c_int] * 8 + [c_void_p] * 4),
     "semidetr_msda_mask_extents": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
     "semidetr_msda_last_kernels": (ctypes.c_char_p, []),
     "semidetr_msda_forward_h16": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
@@ -130,6 +135,8 @@ SIGNATURES = {
     "semidetr_msda_forward_policy_state": (c_int, [c_void_p] * 4),
     "semidetr_msda_forward_policy_state_slot": (c_int, [c_int] + [c_void_p] * 4),
     "semidetr_msda_gather_choice": (c_int, [c_int]),
+    "semidetr_msda_set_region_grid": (c_int, [c_int] * 3),
+    "semidetr_msda_region_grid_query": (c_int, [c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
     "semidetr_match_cost_f32": (c_int, [c_void_p] * 7 + [c_int] * 4 + [POINTER(CostParams), c_void_p]),
     "semidetr_lsap_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "semidetr_lsap_solve": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6),
@@ -335,6 +342,29 @@ def forward_policy_state(slot=0):
     check(lib().semidetr_msda_forward_policy_state_slot(int(slot), ctypes.byref(pol), ctypes.byref(mode), ctypes.byref(frac),
                                                         ctypes.byref(upd)), "semidetr_msda_forward_policy_state_slot")
     return {"policy": pol.value, "mode": mode.value, "far_fraction": frac.value, "updates": upd.value}
+
+
+REGION_GRID_KERNELS = {"forward": 0, "gather": 1, "scatter": 2}
+
+
+def set_region_grid(kernel, nry=0, nrx=0):
+    """Pin the region grid of an encoder window kernel ("forward", "gather" or "scatter"); 0, 0: chosen per launch
+    (include/semidetr_hip.h, semidetr_msda_set_region_grid)."""
+    check(lib().semidetr_msda_set_region_grid(REGION_GRID_KERNELS.get(kernel, kernel), int(nry), int(nrx)),
+          "semidetr_msda_set_region_grid")
+
+
+def region_grid(kernel, spatial_shapes, batch, num_heads, num_cus):
+    """What a launch of ``kernel`` takes for the level table ``spatial_shapes`` (rows of (H, W), or None: no host table):
+    {'nry', 'nrx' (0, 0: the kernel's own coarsest grid), 'regions' (0: unknown), 'workgroups', 'tail_split', 'max_queries'}.
+    Needs no GPU (semidetr_msda_region_grid_query)."""
+    flat = None if spatial_shapes is None else [int(v) for hw in spatial_shapes for v in hw]
+    table = None if flat is None else (c_int64 * len(flat))(*flat)
+    levels = 1 if flat is None else len(flat) // 2
+    out = (c_int * 6)()
+    check(lib().semidetr_msda_region_grid_query(REGION_GRID_KERNELS.get(kernel, kernel), table, levels, int(batch), int(num_heads),
+                                                int(num_cus), out), "semidetr_msda_region_grid_query")
+    return dict(zip(("nry", "nrx", "regions", "workgroups", "tail_split", "max_queries"), out))
 
 
 def set_variant(fwd, bwd):

@@ -531,6 +531,180 @@ constexpr int kRwProduct5 = rw_tune(kRwCompact | kRwQueryList | kRwLevelTable | 
 static_assert(kRwProduct4 == 98320 && kRwProduct5 == 47910, "the product configurations keep their historical numbers");
 static_assert(rw_tune_or(kRwProduct4, kRwTailSplit) == 200720, "... and the tail-split variant its own (98320 + 100 x kRwTailSplit)");
 
+// ---- the region grid of the three encoder window kernels, chosen per launch on the host.
+// msda_rw_d32, msda_gw_d32 and msda_bwd_scatter_d32_reg cut the finest level into regions, one workgroup per (image, region, head).  The
+// windows are sized for regions of up to RTH x RTW pixels, so ceil(H / RTH) x ceil(W / RTW) is the COARSEST grid; any finer one is correct
+// too (smaller regions, wider effective margin) and is a launch argument (grid_ry, grid_rx).  One workgroup per CU (the scatter: two) makes
+// a launch cost ceil(units / slots) unit times, so where the caller hands over a host copy of the level table (the `_v2` entry points)
+// the grid is picked to fill whole waves of workgroups: score = ceil(N * regions * M / slots) * (set-up + rounds(queries of the largest region)).
+// Without a table the launch is what it was: the coarsest grid, the grid size a hint.
+// Measured (profiles/region_grid_probe.txt, 800 x 1333 pyramid, fused prologue + mask, 256 CUs): launches of one image gain -- forward 4 x 11 with
+// the tail split 50.8 -> 4 x 16 without 48.1 us, window gather 7 x 11 -> 8 x 12: the backward 182.5 -> 176.0 us; launches of four images
+// (5.5 waves: the workgroups no longer finish in step, the wave count stops mattering and every extra region only adds set-ups) do not --
+// forward 4 x 11 159.0, 4 x 12 161.6, 4 x 16 170.8 us; gather 7 x 11 551.7, 8 x 12 562.5 us; and the scatter, bound by its row atomics,
+// gains at neither size (one image 13 x 7 175.1, 16 x 8 176.1, 13 x 9 172.6 us; four images every finer grid +2 .. +22 %).
+constexpr int kGridKernels = 3;            // SEMIDETR_MSDA_GRID_FORWARD / _GATHER / _SCATTER
+constexpr int kGridCap = 8;                // grids of up to this many region rows / columns above the coarsest are scored
+constexpr int kGridMaxAxis = 0x7fff;       // a pinned count beyond the level's pixels is legal (regions without a level-0 pixel), up to this
+struct GridGeom {
+    int rth, rtw;          // the kernel's largest region
+    int round;             // queries per round (forward: threads / 8, gather: rows per wave x waves) or per pass (scatter)
+    int per_cu;            // workgroups per CU
+    float setup;           // a unit's set-up (windows staged, lists built, rows flushed) in units of one full round / pass
+    bool even;             // the coarsest grid is tiled evenly (the scatter's steps RTH x RTW and leaves the remainder at the edges)
+};
+// The set-up shares, fitted to the one-image sweep of profiles/region_grid_probe.txt with rounds counted FRACTIONALLY (a round's cost follows
+// the queries in it: 402 queries = 4.2 rounds of 96 cost 3 % more than 374 = 3.9, not a fifth round):
+//   forward  0.5 round of 96 (the windows of the coarse levels; also what a part of a split unit pays again, msda_rw.h): unit times 24.0 / 17.2 us
+//            at 3.9 / 2.66 rounds -> 5.0 us per round + 2.7 us; the grids rank as measured (4 x 16 < 5 x 12 < 4 x 14 < 4 x 13 < 6 x 16 < 7 x 13)
+//   gather   3 rounds of 64 (its windows cover level 0 too, and the far lists are rebuilt per region): 7 x 11 / 8 x 12 / 10 x 12 = 64.8 / 58.3 / 66.2 us
+//            against 24.2 / 20.6 / 23.9 model units
+//   scatter  0.45 of a 256-query pass (count / scan / fill of the window rows and the flush do not shrink with the region: round 5's 8 x 16
+//            regions cost +10 % at bs 4 for 2/3 of the queries) -- not confirmed by the sweep: no grid won, both classes keep the coarsest grid
+GridGeom grid_geom(int kernel, int L)
+{
+    if (kernel == 0) return L == 5 ? GridGeom{SEMIDETR_RW_RTH5, 16, SEMIDETR_RW_NT5 / 8, 1, 0.5f, true}
+                                   : GridGeom{SEMIDETR_RW_RTH, 16, SEMIDETR_RW_NT / 8, 1, 0.5f, true};
+    if (kernel == 1) return L == 5 ? GridGeom{SEMIDETR_GW_RTH5, SEMIDETR_GW_RTW, (SEMIDETR_GW_NT5 / 64) * 3, 1, 3.0f, true}
+                                   : GridGeom{SEMIDETR_GW_RTH, SEMIDETR_GW_RTW, (SEMIDETR_GW_NT / 64) * 4, 1, 3.0f, true};
+    return GridGeom{SEMIDETR_SCATTER_RTH, SEMIDETR_SCATTER_RTW, SEMIDETR_SCATTER_Q, 2, 0.45f, false};
+}
+// Which (kernel, launch class) takes a chosen grid: [kernel][0] launches of fewer than three waves of the coarsest grid's units (one image), [1] larger
+// ones.  A class whose best grid did not beat the coarsest by more than the run-to-run spread keeps the coarsest grid (profiles/region_grid_probe.txt).
+constexpr bool kGridAuto[kGridKernels][2] = {{true, false}, {true, false}, {false, false}};
+struct GridChoice {
+    int nry = 0, nrx = 0;      // what the kernel is given (0 / 0: its own coarsest grid, tiled as before)
+    int regions = 0;           // exact region count of that grid (0: level table unknown, the grid size stays a hint)
+    bool tail = false;         // forward, four levels: helper workgroups for the last wave
+    int max_queries = 0;       // queries of the largest region (0: unknown)
+};
+std::atomic<int> g_grid_pin[kGridKernels];      // nry << 16 | nrx, 0: automatic (semidetr_msda_set_region_grid)
+
+// smallest q in [0, nq] whose pixel centre maps into row >= bound of the nb-row grid level (rw_first on the host)
+int64_t grid_first(int64_t bound, int64_t nq, int64_t nb) { return std::min(nq, ((2 * nq * bound + nb - 1) / nb) >> 1); }
+
+// queries of the largest region of an nry x nrx grid on level `lb` of the host table (H, W pairs); `even`: balanced tiling, else steps of rth x rtw
+int grid_max_queries(const int64_t *hs, int L, int lb, int nry, int nrx, bool even, int rth, int rtw)
+{
+    const int64_t Hb = hs[2 * lb], Wb = hs[2 * lb + 1];
+    std::vector<int> cy((size_t)L * nry), cx((size_t)L * nrx);
+    for (int l = 0; l < L; ++l) {
+        const int64_t Hq = hs[2 * l], Wq = hs[2 * l + 1];
+        for (int r = 0; r < nry; ++r) {
+            const int64_t y0 = even ? r * Hb / nry : (int64_t)r * rth, y1 = even ? (r + 1) * Hb / nry : std::min<int64_t>(y0 + rth, Hb);
+            cy[(size_t)l * nry + r] = (int)std::max<int64_t>((y1 >= Hb ? Hq : grid_first(y1, Hq, Hb)) - grid_first(y0, Hq, Hb), 0);
+        }
+        for (int r = 0; r < nrx; ++r) {
+            const int64_t x0 = even ? r * Wb / nrx : (int64_t)r * rtw, x1 = even ? (r + 1) * Wb / nrx : std::min<int64_t>(x0 + rtw, Wb);
+            cx[(size_t)l * nrx + r] = (int)std::max<int64_t>((x1 >= Wb ? Wq : grid_first(x1, Wq, Wb)) - grid_first(x0, Wq, Wb), 0);
+        }
+    }
+    int best = 0;
+    for (int ry = 0; ry < nry; ++ry)
+        for (int rx = 0; rx < nrx; ++rx) {
+            int q = 0;
+            for (int l = 0; l < L; ++l) q += cy[(size_t)l * nry + ry] * cx[(size_t)l * nrx + rx];
+            best = std::max(best, q);
+        }
+    return best;
+}
+
+// the launch's cost in rounds; `tail` in: the kernel has a tail split, out: the split pays
+double grid_score(const GridGeom &g, int64_t units, int cus, int max_queries, bool &tail)
+{
+    const int64_t slots = (int64_t)cus * g.per_cu;
+    const double rounds = (double)max_queries / g.round;
+    const double unit = g.setup + rounds;
+    const int64_t full = units / slots, rem = units % slots;
+    const double plain = (double)(full + (rem > 0)) * unit;
+    if (tail) {
+        tail = false;
+        // (msda_rw.h: launches of fewer than three waves, the last wave's units cut into s <= 4 parts of their rounds, each staging the windows
+        //  again; + 1 round for the helpers' late start: 4 x 11 / 4 x 12 / 4 x 17 / 5 x 13 with the split measured 9.3 / 9.5 / 9.6 / 9.6 model
+        //  units beside 4 x 16's 8.8 without it, the formula gives 10.3 / 9.4 / 10.4 / 10.7)
+        const int s = rem > 0 ? (int)std::min<int64_t>(slots / rem, 4) : 1;
+        if (units < 3 * slots && s > 1) {
+            const double split = full * unit + g.setup + rounds / s + 1.0;
+            if (split < plain) {
+                tail = true;
+                return split;
+            }
+        }
+    }
+    return plain;
+}
+
+struct GridCacheEntry {
+    int kernel, L, N, M, cus;
+    int64_t hw[2 * 8];
+    GridChoice choice;
+};
+std::mutex g_grid_mu;
+std::vector<GridCacheEntry> g_grid_cache;
+
+// The grid of one launch.  hs: host copy of spatial_shapes (num_levels x {H, W}) or null.  tail_kernel: the configuration has a tail split.
+GridChoice region_grid_choice(int kernel, const int64_t *hs, int L, int N, int M, int cus, bool tail_kernel)
+{
+    GridChoice c;
+    const GridGeom g = grid_geom(kernel, L);
+    const int pin = g_grid_pin[kernel].load(std::memory_order_relaxed);
+    bool known = hs != nullptr && cus > 0 && L > 0 && L <= 8 && N > 0 && M > 0;
+    for (int l = 0; known && l < L; ++l) known = hs[2 * l] > 0 && hs[2 * l] <= 32766 && hs[2 * l + 1] > 0 && hs[2 * l + 1] <= 32766;
+    if (!known) {      // the kernel derives its grid from the device table (a pinned grid: max(pin, coarsest)); grid size by hint
+        c.nry = pin >> 16;
+        c.nrx = pin & 0xffff;
+        return c;
+    }
+    // the level that carries the grid: level 0 for the window kernels, the one with the most pixels for the scatter
+    int lb = 0;
+    if (kernel == 2)
+        for (int l = 1; l < L; ++l)
+            if (hs[2 * l] * hs[2 * l + 1] > hs[2 * lb] * hs[2 * lb + 1]) lb = l;
+    const int Hb = (int)hs[2 * lb], Wb = (int)hs[2 * lb + 1];
+    const int ny0 = (Hb + g.rth - 1) / g.rth, nx0 = (Wb + g.rtw - 1) / g.rtw;
+    auto finish = [&](int ny, int nx, bool as_coarsest) {
+        const bool even = !as_coarsest || g.even;
+        c.nry = as_coarsest && !g.even ? 0 : ny;
+        c.nrx = as_coarsest && !g.even ? 0 : nx;
+        c.regions = ny * nx;
+        c.max_queries = grid_max_queries(hs, L, lb, ny, nx, even, g.rth, g.rtw);
+        bool t = tail_kernel;
+        (void)grid_score(g, (int64_t)N * c.regions * M, cus, c.max_queries, t);
+        c.tail = t;
+    };
+    if (pin) {
+        finish(std::max(pin >> 16, ny0), std::max(pin & 0xffff, nx0), false);
+        return c;
+    }
+    {
+        std::lock_guard<std::mutex> lock(g_grid_mu);
+        for (const auto &e : g_grid_cache)
+            if (e.kernel == kernel && e.L == L && e.N == N && e.M == M && e.cus == cus && std::equal(hs, hs + 2 * L, e.hw)) return e.choice;
+    }
+    finish(ny0, nx0, true);
+    bool t0 = tail_kernel;
+    const double coarse = grid_score(g, (int64_t)N * ny0 * nx0 * M, cus, c.max_queries, t0);
+    const bool small = (int64_t)N * ny0 * nx0 * M < (int64_t)3 * cus * g.per_cu;
+    if (kGridAuto[kernel][small ? 0 : 1]) {
+        double best = coarse * 0.98;      // ties, and gains the model cannot tell from nothing, keep the coarsest grid
+        int by = 0, bx = 0;
+        for (int ny = ny0; ny <= std::min(ny0 + kGridCap, Hb); ++ny)
+            for (int nx = nx0; nx <= std::min(nx0 + kGridCap, Wb); ++nx) {
+                if (ny == ny0 && nx == nx0 && g.even) continue;
+                bool t = tail_kernel;
+                const double s = grid_score(g, (int64_t)N * ny * nx * M, cus, grid_max_queries(hs, L, lb, ny, nx, true, g.rth, g.rtw), t);
+                if (s < best) { best = s; by = ny; bx = nx; }
+            }
+        if (by) finish(by, bx, false);
+    }
+    GridCacheEntry e{kernel, L, N, M, cus, {0}, c};
+    std::copy(hs, hs + 2 * L, e.hw);
+    std::lock_guard<std::mutex> lock(g_grid_mu);
+    if (g_grid_cache.size() >= 64) g_grid_cache.erase(g_grid_cache.begin());
+    g_grid_cache.push_back(e);
+    return c;
+}
+
 // One product configuration of the window forward, keyed on (IO, levels, padding mask): kernel, tail-split kernel, LDS bytes, threads and
 // region pixels all come from the ONE parameter set below, so what is launched and what it is given cannot disagree.
 // Level 0 through global loads, windows of the coarse levels with the widest margin that fits beside the octet records: one workgroup per CU
@@ -568,7 +742,7 @@ struct RwProduct {
 template <typename IO>
 int launch_fast_forward(hipStream_t st, const float *value, const int64_t *spatial_shapes,
                         const int64_t *level_start, const IO &io, int N, int S, int M, int L, int Lq, int P,
-                        int flags, float *out)
+                        int flags, float *out, const int64_t *host_shapes = nullptr)
 {
     SEMIDETR_REQUIRE(!(flags & SEMIDETR_MSDA_QUERIES_ARE_PIXELS) || Lq == S, SEMIDETR_E_BADARG,
                      "msda_forward: SEMIDETR_MSDA_QUERIES_ARE_PIXELS needs num_query == spatial_size");
@@ -600,13 +774,20 @@ int launch_fast_forward(hipStream_t st, const float *value, const int64_t *spati
                 constexpr int threads = C::threads, region_px = C::region_px;
                 // grid sizing hint: the finest level of a DETR pyramid holds ~3/4 of the pixels; a workgroup takes regions slot,
                 // slot + bound, ... so any bound >= 1 is correct (the level table lives in device memory)
-                const int wbound = ((S * 3 / 4 + region_px - 1) / region_px) * 9 / 8 + 2 * L;
+                // -- unless the caller handed over a host copy of the table: then the grid is chosen for this launch (region_grid_choice) and
+                // exactly N x regions x M workgroups are launched
+                const bool tail_kernel = SEMIDETR_RW_TAIL && kern_tail != nullptr;
+                const int dev_cus = device_cus();
+                const GridChoice gc = region_grid_choice(0, host_shapes, L, N, M, dev_cus, tail_kernel);
+                const int wbound = gc.regions ? gc.regions : ((S * 3 / 4 + region_px - 1) / region_px) * 9 / 8 + 2 * L;
                 // + one helper workgroup per CU for the tail split (msda_rw.h: the units of the last, partly filled wave of workgroups are
                 // cut into parts; one workgroup per CU is what the kernel's LDS allows).  SEMIDETR_RW_TAIL=0 builds do without.
                 // Only launches of fewer than ~three waves of workgroups get them (the kernel's own rule, from the real region count): on a
                 // bs-4 launch 256 idle helpers, each waiting for a whole CU to read the level table and leave, cost 7 us of 154.
-                const int cus = (SEMIDETR_RW_TAIL && kern_tail != nullptr) ? device_cus() : 0;
-                const int tail = (int64_t)N * M * ((S * 3 / 4 + region_px - 1) / region_px) < (int64_t)3 * cus ? cus : 0;
+                // (level table known: where the chooser's model says the split pays for the grid it picked)
+                const int cus = tail_kernel ? dev_cus : 0;
+                const int tail = gc.regions ? (gc.tail ? cus : 0)
+                                            : ((int64_t)N * M * ((S * 3 / 4 + region_px - 1) / region_px) < (int64_t)3 * cus ? cus : 0);
                 if (tail > 0) kern = kern_tail;
                 if (int rc = allow_big_lds(kern, wlds, "msda_forward")) {      // refused for this instantiation: the patch kernel below
                     fell_back = true;
@@ -614,7 +795,7 @@ int launch_fast_forward(hipStream_t st, const float *value, const int64_t *spati
                 }
                 SEMIDETR_REQUIRE((int64_t)N * wbound * M + tail < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_forward: grid too large");
                 hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)N * wbound * M + tail)), dim3(threads), wlds, st, (const float *)nullptr,
-                                   value, spatial_shapes, level_start, io, S, M, wbound, out, (float4 *)nullptr, (int64_t)0, fs, tail);
+                                   value, spatial_shapes, level_start, io, S, M, wbound, out, (float4 *)nullptr, (int64_t)0, fs, tail, gc.nry, gc.nrx);
                 g_last_kernels = "msda_rw_d32";
                 return semidetr::launch_status("msda_rw_d32<forward>");
             };
@@ -658,7 +839,7 @@ int launch_fast_forward(hipStream_t st, const float *value, const int64_t *spati
 template <typename IO>
 int launch_fast_backward(hipStream_t st, const float *grad_out, const float *value, const int64_t *spatial_shapes,
                          const int64_t *level_start, const IO &io, int N, int S, int M, int L, int Lq, int P,
-                         int flags, float *grad_value)
+                         int flags, float *grad_value, const int64_t *host_shapes = nullptr)
 {
     SEMIDETR_REQUIRE(!(flags & SEMIDETR_MSDA_QUERIES_ARE_PIXELS) || Lq == S, SEMIDETR_E_BADARG,
                      "msda_backward: SEMIDETR_MSDA_QUERIES_ARE_PIXELS needs num_query == spatial_size");
@@ -704,10 +885,12 @@ int launch_fast_backward(hipStream_t st, const float *grad_out, const float *val
                     (void)hipGetLastError();
                     return false;
                 }
-                const int wbound = ((S * 3 / 4 + region_px - 1) / region_px) * 9 / 8 + 2 * L;
+                // (the region grid and, with the level table on the host, the exact grid size: region_grid_choice)
+                const GridChoice gc = region_grid_choice(1, host_shapes, L, N, M, device_cus(), false);
+                const int wbound = gc.regions ? gc.regions : ((S * 3 / 4 + region_px - 1) / region_px) * 9 / 8 + 2 * L;
                 if ((int64_t)N * wbound * M >= INT32_MAX) return false;
                 hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)N * wbound * M)), dim3(kGwNT), wl, st, grad_out, value, spatial_shapes,
-                                   level_start, io, S, M, wbound, zero, (int64_t)(fill / 16));
+                                   level_start, io, S, M, wbound, zero, (int64_t)(fill / 16), gc.nry, gc.nrx);
                 return true;
             };
             constexpr int kNT5 = std::is_same<IO, RawIO>::value ? SEMIDETR_GW_NT5_RAW : SEMIDETR_GW_NT5;
@@ -769,11 +952,14 @@ int launch_fast_backward(hipStream_t st, const float *grad_out, const float *val
         // a workgroup takes regions slot, slot + bound, ...).  The old hint (S / region * 5 / 4 + 4 L = 161 for the 91 regions of the 800 x
         // 1333 pyramid) launched 2240 workgroups per bs-4 launch that found no region -- each holds one of a CU's two slots until it has read
         // the level table.
-        const int rbound = SEMIDETR_SCATTER_TIGHT ? ((S * 3 / 4 + kRegPix - 1) / kRegPix) * 9 / 8 + 2 * L : (S + kRegPix - 1) / kRegPix * 5 / 4 + 4 * L;
+        // With the level table on the host the region grid is chosen for this launch and the grid size is exact (region_grid_choice).
+        const GridChoice gc = region_grid_choice(2, host_shapes, L, N, M, device_cus(), false);
+        const int rbound = gc.regions ? gc.regions
+                           : (SEMIDETR_SCATTER_TIGHT ? ((S * 3 / 4 + kRegPix - 1) / kRegPix) * 9 / 8 + 2 * L : (S + kRegPix - 1) / kRegPix * 5 / 4 + 4 * L);
         const int64_t rgrid = (int64_t)N * rbound * M;
         SEMIDETR_REQUIRE(rgrid < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_backward: grid too large");
         hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(SEMIDETR_SCATTER_NT), rlds, st, grad_out, spatial_shapes, level_start, io, S, M, L,
-                           rbound, grad_value);
+                           rbound, grad_value, gc.nry, gc.nrx);
         g_last_kernels = window_gather ? "msda_gw_d32+msda_bwd_scatter_d32_reg"
                          : (fill_in_gather ? "msda_bwd_gather_d32+msda_bwd_scatter_d32_reg"
                                            : "fillBufferAligned+msda_bwd_gather_d32+msda_bwd_scatter_d32_reg");
@@ -862,6 +1048,36 @@ extern "C" int semidetr_msda_set_forward_policy(int policy)
     return SEMIDETR_OK;
 }
 
+extern "C" int semidetr_msda_set_region_grid(int kernel, int nry, int nrx)
+{
+    SEMIDETR_REQUIRE(kernel >= 0 && kernel < kGridKernels, SEMIDETR_E_BADARG, "msda_set_region_grid: kernel 0 forward, 1 gather, 2 scatter");
+    SEMIDETR_REQUIRE(nry >= 0 && nrx >= 0 && nry <= kGridMaxAxis && nrx <= kGridMaxAxis && (nry > 0) == (nrx > 0), SEMIDETR_E_BADARG,
+                     "msda_set_region_grid: nry and nrx both 0 (automatic) or both in 1..%d", kGridMaxAxis);
+    SEMIDETR_REQUIRE((int64_t)nry * nrx <= (1 << 22), SEMIDETR_E_TOOLARGE, "msda_set_region_grid: more than %d regions", 1 << 22);
+    g_grid_pin[kernel].store(nry << 16 | nrx, std::memory_order_relaxed);
+    return SEMIDETR_OK;
+}
+
+extern "C" int semidetr_msda_region_grid_query(int kernel, const int64_t *host_spatial_shapes, int num_levels, int batch, int num_heads,
+                                               int num_cus, int *grid6)
+{
+    SEMIDETR_REQUIRE(kernel >= 0 && kernel < kGridKernels, SEMIDETR_E_BADARG, "msda_region_grid_query: kernel 0 forward, 1 gather, 2 scatter");
+    SEMIDETR_REQUIRE(grid6 && num_levels > 0 && batch > 0 && num_heads > 0 && num_cus >= 0, SEMIDETR_E_BADARG,
+                     "msda_region_grid_query: null result or non-positive size (num_levels=%d batch=%d num_heads=%d)", num_levels, batch,
+                     num_heads);
+    const GridChoice c = region_grid_choice(kernel, host_spatial_shapes, num_levels, batch, num_heads, num_cus,
+                                            kernel == 0 && num_levels == 4 && SEMIDETR_RW_TAIL);
+    const int64_t wgs = (int64_t)batch * c.regions * num_heads;
+    SEMIDETR_REQUIRE(wgs + num_cus < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_region_grid_query: grid too large");
+    grid6[0] = c.nry;
+    grid6[1] = c.nrx;
+    grid6[2] = c.regions;
+    grid6[3] = (int)wgs;
+    grid6[4] = c.regions && c.tail ? 1 : 0;
+    grid6[5] = c.max_queries;
+    return SEMIDETR_OK;
+}
+
 extern "C" int semidetr_msda_forward_policy_state_slot(int slot, int *policy, int *mode, float *far_fraction, unsigned *updates)
 {
     SEMIDETR_REQUIRE(slot >= 0 && slot < kPolicySlots, SEMIDETR_E_BADARG, "msda_forward_policy_state: slot must be 0..%d", kPolicySlots - 1);
@@ -917,30 +1133,31 @@ extern "C" void semidetr_msda_set_variant(int fwd_variant, int bwd_variant)
 // fast path of the f32 entry points: the product dispatch, or (experiments library, a variant forced) the tuning dispatch
 template <typename IO>
 static int dispatch_fast_forward(hipStream_t st, const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
-                                 const IO &io, int N, int S, int M, int L, int Lq, int P, int flags, float *out)
+                                 const IO &io, int N, int S, int M, int L, int Lq, int P, int flags, float *out,
+                                 const int64_t *host_shapes)
 {
 #if SEMIDETR_EXPERIMENTS
     if (SEMIDETR_FWD_VARIANT != 0) return exp_launch_fast_forward(st, value, spatial_shapes, level_start, io, N, S, M, L, Lq, P, flags, out);
 #endif
-    return launch_fast_forward(st, value, spatial_shapes, level_start, io, N, S, M, L, Lq, P, flags, out);
+    return launch_fast_forward(st, value, spatial_shapes, level_start, io, N, S, M, L, Lq, P, flags, out, host_shapes);
 }
 template <typename IO>
 static int dispatch_fast_backward(hipStream_t st, const float *grad_out, const float *value, const int64_t *spatial_shapes,
                                   const int64_t *level_start, const IO &io, int N, int S, int M, int L, int Lq, int P, int flags,
-                                  float *grad_value)
+                                  float *grad_value, const int64_t *host_shapes)
 {
 #if SEMIDETR_EXPERIMENTS
     if (SEMIDETR_BWD_VARIANT != 0)
         return exp_launch_fast_backward(st, grad_out, value, spatial_shapes, level_start, io, N, S, M, L, Lq, P, flags, grad_value);
 #endif
-    return launch_fast_backward(st, grad_out, value, spatial_shapes, level_start, io, N, S, M, L, Lq, P, flags, grad_value);
+    return launch_fast_backward(st, grad_out, value, spatial_shapes, level_start, io, N, S, M, L, Lq, P, flags, grad_value, host_shapes);
 }
 
-extern "C" int semidetr_msda_forward_f32(void *stream, const float *value, const int64_t *spatial_shapes,
-                                         const int64_t *level_start, const float *sampling_loc,
-                                         const float *attn_weight, int batch, int spatial_size,
-                                         int num_heads, int channels, int num_levels, int num_query,
-                                         int num_point, int flags, float *out)
+extern "C" int semidetr_msda_forward_f32_v2(void *stream, const float *value, const int64_t *spatial_shapes,
+                                            const int64_t *level_start, const float *sampling_loc,
+                                            const float *attn_weight, int batch, int spatial_size,
+                                            int num_heads, int channels, int num_levels, int num_query,
+                                            int num_point, int flags, float *out, const int64_t *host_spatial_shapes)
 {
     const int N = batch, S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query,
               P = num_point;
@@ -953,15 +1170,25 @@ extern "C" int semidetr_msda_forward_f32(void *stream, const float *value, const
     SEMIDETR_REQUIRE(out, SEMIDETR_E_BADARG, "msda_forward: null output");
     const LocAttnIO io = {sampling_loc, attn_weight, nullptr, nullptr};
     return dispatch_fast_forward(semidetr::as_stream(stream), value, spatial_shapes, level_start, io, N, S, M, L, Lq,
-                                 P, flags, out);
+                                 P, flags, out, host_spatial_shapes);
 }
 
-extern "C" int semidetr_msda_backward_f32(void *stream, const float *grad_out, const float *value,
-                                          const int64_t *spatial_shapes, const int64_t *level_start,
-                                          const float *sampling_loc, const float *attn_weight, int batch,
-                                          int spatial_size, int num_heads, int channels, int num_levels,
-                                          int num_query, int num_point, int flags, float *grad_value,
-                                          float *grad_sampling_loc, float *grad_attn_weight)
+extern "C" int semidetr_msda_forward_f32(void *stream, const float *value, const int64_t *spatial_shapes,
+                                         const int64_t *level_start, const float *sampling_loc,
+                                         const float *attn_weight, int batch, int spatial_size,
+                                         int num_heads, int channels, int num_levels, int num_query,
+                                         int num_point, int flags, float *out)
+{
+    return semidetr_msda_forward_f32_v2(stream, value, spatial_shapes, level_start, sampling_loc, attn_weight, batch, spatial_size,
+                                        num_heads, channels, num_levels, num_query, num_point, flags, out, nullptr);
+}
+
+extern "C" int semidetr_msda_backward_f32_v2(void *stream, const float *grad_out, const float *value,
+                                             const int64_t *spatial_shapes, const int64_t *level_start,
+                                             const float *sampling_loc, const float *attn_weight, int batch,
+                                             int spatial_size, int num_heads, int channels, int num_levels,
+                                             int num_query, int num_point, int flags, float *grad_value,
+                                             float *grad_sampling_loc, float *grad_attn_weight, const int64_t *host_spatial_shapes)
 {
     const int N = batch, S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query,
               P = num_point;
@@ -977,7 +1204,19 @@ extern "C" int semidetr_msda_backward_f32(void *stream, const float *grad_out, c
                      "msda_backward: null pointer argument");
     const LocAttnIO io = {sampling_loc, attn_weight, grad_sampling_loc, grad_attn_weight};
     return dispatch_fast_backward(semidetr::as_stream(stream), grad_out, value, spatial_shapes, level_start, io, N, S,
-                                  M, L, Lq, P, flags, grad_value);
+                                  M, L, Lq, P, flags, grad_value, host_spatial_shapes);
+}
+
+extern "C" int semidetr_msda_backward_f32(void *stream, const float *grad_out, const float *value,
+                                          const int64_t *spatial_shapes, const int64_t *level_start,
+                                          const float *sampling_loc, const float *attn_weight, int batch,
+                                          int spatial_size, int num_heads, int channels, int num_levels,
+                                          int num_query, int num_point, int flags, float *grad_value,
+                                          float *grad_sampling_loc, float *grad_attn_weight)
+{
+    return semidetr_msda_backward_f32_v2(stream, grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, batch,
+                                         spatial_size, num_heads, channels, num_levels, num_query, num_point, flags, grad_value,
+                                         grad_sampling_loc, grad_attn_weight, nullptr);
 }
 
 // ---- fused MSDeformAttn prologue / epilogue (fp32, channels == 32) --------------------------------------
@@ -997,13 +1236,13 @@ static int check_fused(const void *value, const void *shapes, const void *starts
     return SEMIDETR_OK;
 }
 
-extern "C" int semidetr_msda_fused_forward_f32(void *stream, const float *value, const int64_t *spatial_shapes,
-                                               const int64_t *level_start, const float *reference_points,
-                                               int ref_dim, const float *sampling_offsets,
-                                               const float *attn_logits, const unsigned char *padding_mask,
-                                               const int *mask_extents, int batch,
-                                               int spatial_size, int num_heads, int channels, int num_levels, int num_query,
-                                               int num_point, int flags, float *out)
+extern "C" int semidetr_msda_fused_forward_f32_v2(void *stream, const float *value, const int64_t *spatial_shapes,
+                                                  const int64_t *level_start, const float *reference_points,
+                                                  int ref_dim, const float *sampling_offsets,
+                                                  const float *attn_logits, const unsigned char *padding_mask,
+                                                  const int *mask_extents, int batch,
+                                                  int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                                                  int num_point, int flags, float *out, const int64_t *host_spatial_shapes)
 {
     if (int rc = check_fused(value, spatial_shapes, level_start, reference_points, ref_dim, sampling_offsets,
                              attn_logits, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point))
@@ -1015,17 +1254,31 @@ extern "C" int semidetr_msda_fused_forward_f32(void *stream, const float *value,
     SEMIDETR_REQUIRE(!padding_mask || SEMIDETR_FWD_VARIANT == 0, SEMIDETR_E_BADARG,
                      "msda_fused_forward: the experimental kernel variants do not take a padding mask");
     return dispatch_fast_forward(semidetr::as_stream(stream), value, spatial_shapes, level_start, io, batch,
-                                 spatial_size, num_heads, num_levels, num_query, num_point, flags, out);
+                                 spatial_size, num_heads, num_levels, num_query, num_point, flags, out, host_spatial_shapes);
 }
 
-extern "C" int semidetr_msda_fused_backward_f32(void *stream, const float *grad_out, const float *value,
-                                                const int64_t *spatial_shapes, const int64_t *level_start,
-                                                const float *reference_points, int ref_dim,
-                                                const float *sampling_offsets, const float *attn_logits,
-                                                const unsigned char *padding_mask, const int *mask_extents, int batch,
-                                                int spatial_size, int num_heads, int channels, int num_levels,
-                                                int num_query, int num_point, int flags, float *grad_value,
-                                                float *grad_sampling_offsets, float *grad_attn_logits)
+extern "C" int semidetr_msda_fused_forward_f32(void *stream, const float *value, const int64_t *spatial_shapes,
+                                               const int64_t *level_start, const float *reference_points,
+                                               int ref_dim, const float *sampling_offsets,
+                                               const float *attn_logits, const unsigned char *padding_mask,
+                                               const int *mask_extents, int batch,
+                                               int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                                               int num_point, int flags, float *out)
+{
+    return semidetr_msda_fused_forward_f32_v2(stream, value, spatial_shapes, level_start, reference_points, ref_dim, sampling_offsets,
+                                              attn_logits, padding_mask, mask_extents, batch, spatial_size, num_heads, channels,
+                                              num_levels, num_query, num_point, flags, out, nullptr);
+}
+
+extern "C" int semidetr_msda_fused_backward_f32_v2(void *stream, const float *grad_out, const float *value,
+                                                   const int64_t *spatial_shapes, const int64_t *level_start,
+                                                   const float *reference_points, int ref_dim,
+                                                   const float *sampling_offsets, const float *attn_logits,
+                                                   const unsigned char *padding_mask, const int *mask_extents, int batch,
+                                                   int spatial_size, int num_heads, int channels, int num_levels,
+                                                   int num_query, int num_point, int flags, float *grad_value,
+                                                   float *grad_sampling_offsets, float *grad_attn_logits,
+                                                   const int64_t *host_spatial_shapes)
 {
     if (int rc = check_fused(value, spatial_shapes, level_start, reference_points, ref_dim, sampling_offsets,
                              attn_logits, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point))
@@ -1040,7 +1293,22 @@ extern "C" int semidetr_msda_fused_backward_f32(void *stream, const float *grad_
     SEMIDETR_REQUIRE(!padding_mask || SEMIDETR_BWD_VARIANT == 0, SEMIDETR_E_BADARG,
                      "msda_fused_backward: the experimental kernel variants do not take a padding mask");
     return dispatch_fast_backward(semidetr::as_stream(stream), grad_out, value, spatial_shapes, level_start, io, batch,
-                                  spatial_size, num_heads, num_levels, num_query, num_point, flags, grad_value);
+                                  spatial_size, num_heads, num_levels, num_query, num_point, flags, grad_value, host_spatial_shapes);
+}
+
+extern "C" int semidetr_msda_fused_backward_f32(void *stream, const float *grad_out, const float *value,
+                                                const int64_t *spatial_shapes, const int64_t *level_start,
+                                                const float *reference_points, int ref_dim,
+                                                const float *sampling_offsets, const float *attn_logits,
+                                                const unsigned char *padding_mask, const int *mask_extents, int batch,
+                                                int spatial_size, int num_heads, int channels, int num_levels,
+                                                int num_query, int num_point, int flags, float *grad_value,
+                                                float *grad_sampling_offsets, float *grad_attn_logits)
+{
+    return semidetr_msda_fused_backward_f32_v2(stream, grad_out, value, spatial_shapes, level_start, reference_points, ref_dim,
+                                               sampling_offsets, attn_logits, padding_mask, mask_extents, batch, spatial_size, num_heads,
+                                               channels, num_levels, num_query, num_point, flags, grad_value, grad_sampling_offsets,
+                                               grad_attn_logits, nullptr);
 }
 
 // ---- padding mask -> one word per (image, level): vh | vw << 16 or -1 (MaskExt, msda_fast.h).  One workgroup per (image, level): the first

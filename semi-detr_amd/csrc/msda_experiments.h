@@ -25,7 +25,7 @@ int launch_rw(hipStream_t st, const float *grad_out, const float *value, const i
     constexpr size_t lds = rw_lds_bytes<NT, RTH, RTW, H0, HC, KL, TUNE>();
     static_assert(lds <= 160 * 1024, "region-window configuration does not fit the LDS");
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, st, grad_out, value, spatial_shapes, level_start, io, S, M,
-                       bound, out, zero, zero_n4, FwdStats{nullptr, 0u}, 0);
+                       bound, out, zero, zero_n4, FwdStats{nullptr, 0u}, 0, 0, 0);
     return semidetr::launch_status(GATHER ? "msda_rw_d32<gather>" : "msda_rw_d32<forward>");
 }
 
@@ -640,14 +640,14 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
                 }                                                                                                        \
                 const size_t rlds = reg_lds_bytes<NT_, Q_, WH_, WW_>();                                                  \
                 hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(NT_), rlds, st, grad_out, spatial_shapes, level_start, \
-                                   io, S, M, L, rbound, grad_value);                                                    \
+                                   io, S, M, L, rbound, grad_value, 0, 0);                                                    \
             } while (0)
             if (g_bwd_variant == 696) {                                             // instrumented build
                 auto kern = &msda_bwd_scatter_d32_reg<IO, 512, 208, 8, 16, 24, 32, 1>;
                 (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
                 const size_t rlds = reg_lds_bytes<512, 208, 24, 32>();
                 hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(512), rlds, st, grad_out, spatial_shapes, level_start, io, S,
-                                   M, L, rbound, grad_value);
+                                   M, L, rbound, grad_value, 0, 0);
             } else if (g_bwd_variant == 6988 || g_bwd_variant == 6989) {            // timing aids: no second-row flushes / no misses
                 const size_t rlds = reg_lds_bytes<512, 176, 24, 32>();
                 if (g_bwd_variant == 6988)
@@ -665,11 +665,11 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
                 if (g_bwd_variant == 6960) {
                     auto kern = &msda_bwd_scatter_d32_reg<IO, 512, 176, 8, 16, 24, 32, 1, 6, 8>;
                     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-                    hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(512), rlds, st, grad_out, spatial_shapes, level_start, io, S, M, L, rbound, grad_value);
+                    hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(512), rlds, st, grad_out, spatial_shapes, level_start, io, S, M, L, rbound, grad_value, 0, 0);
                 } else {
                     auto kern = &msda_bwd_scatter_d32_reg<IO, 512, 176, 8, 16, 24, 32, 1, 6, kWuPaired + 4>;
                     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-                    hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(512), rlds, st, grad_out, spatial_shapes, level_start, io, S, M, L, rbound, grad_value);
+                    hipLaunchKernelGGL(kern, dim3((unsigned)rgrid), dim3(512), rlds, st, grad_out, spatial_shapes, level_start, io, S, M, L, rbound, grad_value, 0, 0);
                 }
             } else if (g_bwd_variant == 691) LAUNCH_REG(512, 208, 16, 8, 32, 24);   // tuning variants
             else if (g_bwd_variant == 692) LAUNCH_REG(256, 112, 8, 8, 24, 24);

@@ -81,13 +81,24 @@ struct PyramidEntry {
     const void *p_shapes, *p_starts;
     int64_t S;
     int result;
+    int levels;               // rows of `table` (0: the table is not kept -- more than kTableLevels levels)
+    int64_t table[2 * 32];    // the host copy of spatial_shapes the verdict was computed from
+};
+constexpr int kTableLevels = 32;
+// the host copy of spatial_shapes for the `_v2` entry points of the C ABI (they choose the encoder kernels' region grids from it)
+struct HostTable {
+    int levels = 0;
+    int64_t hw[2 * kTableLevels];
+    const int64_t *ptr() const { return levels > 0 ? hw : nullptr; }
 };
 std::mutex g_pyr_mutex;
 std::vector<PyramidEntry> g_pyr_cache;
 
 // bit 0: sum(H*W) == S (the reference's assert); bit 1: level_start tiles [0, S) contiguously
-int pyramid_check(const at::Tensor &shapes, const at::Tensor &starts, int64_t S)
+// table (optional): receives the host copy the verdict rests on -- what the check fetched anyway, no further copy or synchronisation
+int pyramid_lookup(const at::Tensor &shapes, const at::Tensor &starts, int64_t S, HostTable *table)
 {
+    if (table) table->levels = 0;
     auto *is = shapes.unsafeGetTensorImpl();
     auto *it = starts.unsafeGetTensorImpl();
     // Inference tensors have no version counter (torch.inference_mode(): "Inference tensors do not track version
@@ -104,8 +115,13 @@ int pyramid_check(const at::Tensor &shapes, const at::Tensor &starts, int64_t S)
             // checks, that is outside what a version-based cache can notice.)
             if (a && b && e.v_shapes == is->version_counter().current_version() &&
                 e.v_starts == it->version_counter().current_version() && e.p_shapes == shapes.data_ptr() &&
-                e.p_starts == starts.data_ptr())
+                e.p_starts == starts.data_ptr()) {
+                if (table && e.levels > 0) {
+                    table->levels = e.levels;
+                    std::copy(e.table, e.table + 2 * e.levels, table->hw);
+                }
                 return e.result;
+            }
         }
     }
     TORCH_CHECK(shapes.scalar_type() == at::kLong && starts.scalar_type() == at::kLong && shapes.dim() == 2 &&
@@ -127,26 +143,35 @@ int pyramid_check(const at::Tensor &shapes, const at::Tensor &starts, int64_t S)
         sum += ps[2 * l] * ps[2 * l + 1];
     }
     const int result = (sum == S ? 1 : 0) | (tiles && sum == S ? 2 : 0);
+    const int levels = hs.size(0) <= kTableLevels ? (int)hs.size(0) : 0;
+    if (table && levels > 0) {
+        table->levels = levels;
+        std::copy(ps, ps + 2 * levels, table->hw);
+    }
     if (!cacheable) return result;
     std::lock_guard<std::mutex> lock(g_pyr_mutex);
     if (g_pyr_cache.size() >= 16) g_pyr_cache.erase(g_pyr_cache.begin());
     g_pyr_cache.push_back({c10::weak_intrusive_ptr<c10::TensorImpl>(shapes.getIntrusivePtr()),
                            c10::weak_intrusive_ptr<c10::TensorImpl>(starts.getIntrusivePtr()),
                            is->version_counter().current_version(), it->version_counter().current_version(),
-                           shapes.data_ptr(), starts.data_ptr(), S, result});
+                           shapes.data_ptr(), starts.data_ptr(), S, result, levels, {0}});
+    std::copy(ps, ps + 2 * levels, g_pyr_cache.back().table);
     return result;
 }
 
+int pyramid_check(const at::Tensor &shapes, const at::Tensor &starts, int64_t S) { return pyramid_lookup(shapes, starts, S, nullptr); }
+
 // `flags` of the f32 entry points: the self-attention statement, the call site's slot of the forward-kernel choice, and -- while
 // torch.use_deterministic_algorithms(True) is in force -- a forward kernel that does not depend on earlier launches
-int self_attention_flags(const at::Tensor &shapes, const at::Tensor &starts, int Lq, int S, int64_t policy_slot = 0)
+int self_attention_flags(const at::Tensor &shapes, const at::Tensor &starts, int Lq, int S, int64_t policy_slot = 0,
+                         HostTable *table = nullptr)
 {
     // (the backward calls may carry, OR-ed into the slot number, what gather_choice(slot) answered when the matching forward ran:
     //  SEMIDETR_MSDA_GATHER_WINDOW / _PATCH, bits 16 / 17 -- the autograd functions do that)
     constexpr int64_t kGather = SEMIDETR_MSDA_GATHER_WINDOW | SEMIDETR_MSDA_GATHER_PATCH;
     TORCH_CHECK(policy_slot >= 0 && (policy_slot & ~kGather) <= 255 && (policy_slot & kGather) != kGather,
                 "policy_slot must be 0..255 (optionally | gather_choice(slot)), got ", policy_slot);
-    return ((Lq == S && (pyramid_check(shapes, starts, S) & 2)) ? SEMIDETR_MSDA_QUERIES_ARE_PIXELS : 0) |
+    return ((Lq == S && (pyramid_lookup(shapes, starts, S, table) & 2)) ? SEMIDETR_MSDA_QUERIES_ARE_PIXELS : 0) |
            SEMIDETR_MSDA_POLICY_SLOT((int)(policy_slot & 0xff)) | (int)(policy_slot & kGather) |
            (at::globalContext().deterministicAlgorithms() ? SEMIDETR_MSDA_FIXED_FORWARD : 0);
 }
@@ -168,11 +193,13 @@ at::Tensor ms_deform_attn_forward(const at::Tensor &value, const at::Tensor &spa
         rc = semidetr_msda_forward_f64(stream_of(value), value.data_ptr<double>(), sh, ls, sampling_loc.data_ptr<double>(),
                                        attn_weight.data_ptr<double>(), d.N, d.S, d.M, d.D, d.L, d.Lq, d.P,
                                        out.data_ptr<double>());
-    else
-        rc = semidetr_msda_forward_f32(stream_of(value), value.data_ptr<float>(), sh, ls, sampling_loc.data_ptr<float>(),
-                                       attn_weight.data_ptr<float>(), d.N, d.S, d.M, d.D, d.L, d.Lq, d.P,
-                                       self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot),
-                                       out.data_ptr<float>());
+    else {
+        HostTable ht;
+        const int flags = self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot, &ht);
+        rc = semidetr_msda_forward_f32_v2(stream_of(value), value.data_ptr<float>(), sh, ls, sampling_loc.data_ptr<float>(),
+                                          attn_weight.data_ptr<float>(), d.N, d.S, d.M, d.D, d.L, d.Lq, d.P, flags,
+                                          out.data_ptr<float>(), ht.ptr());
+    }
     check_rc(rc, "ms_deform_attn_forward");
     return out;
 }
@@ -200,11 +227,14 @@ std::vector<at::Tensor> ms_deform_attn_backward(const at::Tensor &value, const a
                                         sampling_loc.data_ptr<double>(), attn_weight.data_ptr<double>(), d.N, d.S, d.M,
                                         d.D, d.L, d.Lq, d.P, gv.data_ptr<double>(), gl.data_ptr<double>(),
                                         ga.data_ptr<double>());
-    else
-        rc = semidetr_msda_backward_f32(stream_of(value), grad_output.data_ptr<float>(), value.data_ptr<float>(), sh, ls,
-                                        sampling_loc.data_ptr<float>(), attn_weight.data_ptr<float>(), d.N, d.S, d.M, d.D,
-                                        d.L, d.Lq, d.P, self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot),
-                                        gv.data_ptr<float>(), gl.data_ptr<float>(), ga.data_ptr<float>());
+    else {
+        HostTable ht;
+        const int flags = self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot, &ht);
+        rc = semidetr_msda_backward_f32_v2(stream_of(value), grad_output.data_ptr<float>(), value.data_ptr<float>(), sh, ls,
+                                           sampling_loc.data_ptr<float>(), attn_weight.data_ptr<float>(), d.N, d.S, d.M, d.D,
+                                           d.L, d.Lq, d.P, flags, gv.data_ptr<float>(), gl.data_ptr<float>(), ga.data_ptr<float>(),
+                                           ht.ptr());
+    }
     check_rc(rc, "ms_deform_attn_backward");
     return {gv, gl, ga};
 }
@@ -433,11 +463,13 @@ at::Tensor ms_deform_attn_fused_forward(const at::Tensor &value, const at::Tenso
     const unsigned char *mask = mask_ptr(padding_mask, value, d);
     at::Tensor ext;      // (kept alive until the launch is queued; the allocator orders its reuse on this stream)
     if (mask) ext = mask_extents(*padding_mask, spatial_shapes, level_start_index);
-    const int rc = semidetr_msda_fused_forward_f32(
+    HostTable ht;      // (the host copy of the level table the pyramid check holds anyway: the library chooses the region grids from it)
+    const int flags = self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot, &ht);
+    const int rc = semidetr_msda_fused_forward_f32_v2(
         stream_of(value), value.data_ptr<float>(), spatial_shapes.data_ptr<int64_t>(), level_start_index.data_ptr<int64_t>(),
         ref.data_ptr<float>(), (int)reference_points.size(-1), sampling_offsets.data_ptr<float>(),
         attn_logits.data_ptr<float>(), mask, mask ? ext.data_ptr<int>() : nullptr, d.N, d.S, d.M, d.D, d.L, d.Lq, d.P,
-        self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot), out.data_ptr<float>());
+        flags, out.data_ptr<float>(), ht.ptr());
     check_rc(rc, "ms_deform_attn_fused_forward");
     return out;
 }
@@ -460,12 +492,13 @@ std::vector<at::Tensor> ms_deform_attn_fused_backward(const at::Tensor &value, c
     const unsigned char *mask = mask_ptr(padding_mask, value, d);
     at::Tensor ext;
     if (mask) ext = mask_extents(*padding_mask, spatial_shapes, level_start_index);
-    const int rc = semidetr_msda_fused_backward_f32(
+    HostTable ht;
+    const int flags = self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot, &ht);
+    const int rc = semidetr_msda_fused_backward_f32_v2(
         stream_of(value), grad_output.data_ptr<float>(), value.data_ptr<float>(), spatial_shapes.data_ptr<int64_t>(),
         level_start_index.data_ptr<int64_t>(), ref.data_ptr<float>(), (int)reference_points.size(-1),
         sampling_offsets.data_ptr<float>(), attn_logits.data_ptr<float>(), mask, mask ? ext.data_ptr<int>() : nullptr, d.N, d.S, d.M,
-        d.D, d.L, d.Lq, d.P, self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot), gv.data_ptr<float>(),
-        go.data_ptr<float>(), gl.data_ptr<float>());
+        d.D, d.L, d.Lq, d.P, flags, gv.data_ptr<float>(), go.data_ptr<float>(), gl.data_ptr<float>(), ht.ptr());
     check_rc(rc, "ms_deform_attn_fused_backward");
     return {gv, go, gl};
 }

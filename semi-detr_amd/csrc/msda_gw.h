@@ -94,7 +94,8 @@ __device__ __forceinline__ float gw_row_max(float x, int bp)
 template <typename IO, int NT, int RTH, int RTW, int H0, int HC, int KL, bool MASK = false, int DBG = 0>
 __global__ __launch_bounds__(NT, 1) void msda_gw_d32(
     const float *__restrict__ gout, const float *__restrict__ value, const int64_t *__restrict__ shapes,
-    const int64_t *__restrict__ starts, const IO io, int S, int M, int regions_bound, float4 *__restrict__ zero, int64_t zero_n4)
+    const int64_t *__restrict__ starts, const IO io, int S, int M, int regions_bound, float4 *__restrict__ zero, int64_t zero_n4,
+    int grid_ry = 0, int grid_rx = 0)
 {
     io.same_dims(S, M, KL);
     using Wn = RwWin<RTH, RTW, H0, HC, KL>;
@@ -184,7 +185,8 @@ __global__ __launch_bounds__(NT, 1) void msda_gw_d32(
     const int cls = g >> 3;
 
     const int Hb = Hs[0], Wb = Ws[0];                     // the region grid lives on level 0
-    const int nry = (Hb + RTH - 1) / RTH, nrx = (Wb + RTW - 1) / RTW, nregions = nry * nrx;
+    // (grid_ry x grid_rx: the host's choice for this launch, as in msda_rw_d32; 0 or too coarse for the windows: ceil(H / RTH) x ceil(W / RTW))
+    const int nry = max(grid_ry, (Hb + RTH - 1) / RTH), nrx = max(grid_rx, (Wb + RTW - 1) / RTW), nregions = nry * nrx;
     const __amdgpu_buffer_rsrc_t vr = image_rsrc(value + (int64_t)n * S * M * kD, (unsigned)S * M * kD * 4u);
     const __amdgpu_buffer_rsrc_t gr = image_rsrc(gout + (int64_t)n * Lq * M * kD, (unsigned)Lq * M * kD * 4u);
     const unsigned row_bytes = (unsigned)rs * 4u, head_b = (unsigned)(m * kD) * 4u;

@@ -45,7 +45,7 @@ template <typename IO, int NT, int kRegQ, int RTH, int RTW, int WH, int WW, int 
 __device__ __forceinline__ void reg_scatter_body(
     const int b, float4 *smem, const float *__restrict__ gout, const int64_t *__restrict__ shapes,
     const int64_t *__restrict__ starts, const IO io, int S, int M, int L, int regions_bound, float *__restrict__ gvalue,
-    const float *__restrict__ value = nullptr)
+    const float *__restrict__ value = nullptr, int grid_ry = 0, int grid_rx = 0)
 {
     io.same_dims(S, M, L);
     constexpr int kWR = WH * WW, kNE = kRegQ * kPT * 4, SPT = (kRegQ * kPT + NT - 1) / NT, KC = (kWR + NT - 1) / NT;
@@ -99,7 +99,11 @@ __device__ __forceinline__ void reg_scatter_body(
         if (h * w > Hb * Wb) { lb = l; Hb = h; Wb = w; }
     }
     (void)lb;
-    const int nry = (Hb + RTH - 1) / RTH, nrx = (Wb + RTW - 1) / RTW;
+    // grid_ry x grid_rx (both 0: none): the region grid the host chose for this launch from its copy of the level table (msda.hip
+    // region_grid_choice), tiled EVENLY like the window kernels' and never coarser than ceil(H / RTH) x ceil(W / RTW), which the windows are
+    // sized for.  None: that grid in steps of RTH x RTW, the remainder at the bottom and right edges.
+    const bool even = (grid_ry | grid_rx) != 0;
+    const int nry = max(grid_ry, (Hb + RTH - 1) / RTH), nrx = max(grid_rx, (Wb + RTW - 1) / RTW);
 
     unsigned long long tmark = DBG ? __builtin_readcyclecounter() : 0ull;      // instrumented build: see msda_dest.h
     (void)tmark;                                                               // (the product build's SEMIDETR_DBG_ADD is empty)
@@ -118,8 +122,9 @@ __device__ __forceinline__ void reg_scatter_body(
         int tid_r = fresh_tid(), Hb_p = Hb_k, Wb_p = Wb_k, nrx_p = nrx_k;
         asm volatile("" : "+v"(tid_r), "+s"(Hb_p), "+s"(Wb_p), "+s"(nrx_p));
         const int tid = tid_r, Hb = Hb_p, Wb = Wb_p, nrx = nrx_p;
-        const int y0b = (reg / nrx) * RTH, x0b = (reg % nrx) * RTW;
-        const int y1b = min(y0b + RTH, Hb), x1b = min(x0b + RTW, Wb);
+        const int ry_b = reg / nrx, rx_b = reg % nrx;
+        const int y0b = even ? (ry_b * Hb) / nry : ry_b * RTH, x0b = even ? (rx_b * Wb) / nrx : rx_b * RTW;
+        const int y1b = even ? ((ry_b + 1) * Hb) / nry : min(y0b + RTH, Hb), x1b = even ? ((rx_b + 1) * Wb) / nrx : min(x0b + RTW, Wb);
         __syncthreads();                      // previous region fully done before its LDS state is reused
         // ---- the region's queries: on level lq the pixels whose centre maps into [y0b, y1b) x [x0b, x1b) of the finest
         //      level -- by(qy) = ((2 qy + 1) Hb) / (2 Hq) is monotone, so they form an exact rectangle
@@ -143,8 +148,8 @@ __device__ __forceinline__ void reg_scatter_body(
         // (wave-uniform values that came through vector registers -- an LDS sum, two float divisions -- go back to scalar registers)
         const int nq_total = __builtin_amdgcn_readfirstlane(nq_sum);
         // region centre in normalised coordinates (pixel centres are (i + 0.5) / size)
-        const float pcy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((y0b + 0.5f * RTH) / (float)Hb)));
-        const float pcx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((x0b + 0.5f * RTW) / (float)Wb)));
+        const float pcy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((even ? 0.5f * (float)(y0b + y1b) : y0b + 0.5f * RTH) / (float)Hb)));
+        const float pcx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((even ? 0.5f * (float)(x0b + x1b) : x0b + 0.5f * RTW) / (float)Wb)));
 
         for (int q_base = 0; q_base < nq_total; q_base += kRegQ) {      // one pass unless the region has > kRegQ queries
             const int nq = min(kRegQ, nq_total - q_base);
@@ -735,7 +740,7 @@ __device__ __forceinline__ void reg_scatter_body(
 template <typename IO, int NT, int kRegQ, int RTH, int RTW, int WH, int WW, int DBG = 0, int WPE = 4, int WU = 8>
 __global__ __launch_bounds__(NT, WPE) void msda_bwd_scatter_d32_reg(
     const float *__restrict__ gout, const int64_t *__restrict__ shapes, const int64_t *__restrict__ starts,
-    const IO io, int S, int M, int L, int regions_bound, float *__restrict__ gvalue)
+    const IO io, int S, int M, int L, int regions_bound, float *__restrict__ gvalue, int grid_ry = 0, int grid_rx = 0)
 {
     io.same_dims(S, M, L);
     extern __shared__ float4 smem[];
@@ -743,7 +748,7 @@ __global__ __launch_bounds__(NT, WPE) void msda_bwd_scatter_d32_reg(
 #define SEMIDETR_SCATTER_AID 0      // tuning builds (tools/ab_build.sh -DSEMIDETR_SCATTER_AID=...): timing aids of the walk, results wrong
 #endif
     reg_scatter_body<IO, NT, kRegQ, RTH, RTW, WH, WW, DBG, WU, 0, SEMIDETR_SCATTER_AID>((int)blockIdx.x, smem, gout, shapes, starts, io, S, M, L,
-                                                          regions_bound, gvalue);
+                                                          regions_bound, gvalue, nullptr, grid_ry, grid_rx);
 }
 
 #if SEMIDETR_EXPERIMENTS

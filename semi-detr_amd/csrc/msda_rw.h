@@ -209,7 +209,7 @@ template <typename IO, int NT, int RTH, int RTW, int H0, int HC, int KL, bool GA
 __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(      // 256-thread workgroups: two per CU
     const float *__restrict__ gout, const float *__restrict__ value, const int64_t *__restrict__ shapes,
     const int64_t *__restrict__ starts, const IO io, int S, int M, int regions_bound, float *__restrict__ out,
-    float4 *__restrict__ zero, int64_t zero_n4, const FwdStats fs = FwdStats{nullptr, 0u}, int tail_cus = 0)
+    float4 *__restrict__ zero, int64_t zero_n4, const FwdStats fs = FwdStats{nullptr, 0u}, int tail_cus = 0, int grid_ry = 0, int grid_rx = 0)
 {
     io.same_dims(S, M, KL);
     using Wn = RwWin<RTH, RTW, H0, HC, KL>;
@@ -284,7 +284,9 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
     // the region grid lives on level 0 (the finest level of a DETR pyramid; any order is correct, the windows are sized
     // for this one)
     const int Hb = Hs[0], Wb = Ws[0];
-    const int nry = (Hb + RTH - 1) / RTH, nrx = (Wb + RTW - 1) / RTW;
+    // grid_ry x grid_rx: the region grid the host chose for this launch from its copy of the level table (msda.hip region_grid_choice); 0, or
+    // anything coarser than the windows are sized for: ceil(H / RTH) x ceil(W / RTW).  Finer grids only make the regions smaller.
+    const int nry = max(grid_ry, (Hb + RTH - 1) / RTH), nrx = max(grid_rx, (Wb + RTW - 1) / RTW);
 
     // ---- which (image, head, region) is mine -- and the TAIL SPLIT (round 5).  One workgroup per CU, every (image, head, region) unit
     // about equally long: a launch of U units takes ceil(U / CUs) unit times -- 1408 units on 256 CUs = 6 for 5.5 (bs 4), 352 = 2 for
@@ -400,7 +402,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
     char *const orec = recs + oc * kOctBytes;             // this octet's records
     const char *const wbase = lds + j8 * 16;
 
-    const int Hb_k = Hb, Wb_k = Wb, nrx_k = nrx, nregions = nry * nrx;
+    const int Hb_k = Hb, Wb_k = Wb, nrx_k = nrx, nry_k = nry, nregions = nry * nrx;
     // MASK: a level whose mask is not a summarised band (MaskExt < 0) is handled through its BYTES -- loads inside branches of the staging, the
     // level-0 records and the out-of-window loop.  Never taken for the masks DETR builds, those branches still cost the masked kernel 5 % (190
     // -> 181 us, round 6: every basic-block boundary around a load is a full s_waitcnt, which also drains the prefetched sampling data and the
@@ -409,13 +411,13 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
     auto run_regions = [&](auto bytes_tag) {
     constexpr bool kBytes = MASK && decltype(bytes_tag)::value;
     for (int reg = slot0; reg < nregions; reg += regions_bound) {
-        int Hb_r = Hb_k, Wb_r = Wb_k, nrx_r = nrx_k;      // kRwRebuildTid: ... and the reciprocals of the divisions by these
-        if (T::rebuild_tid) asm volatile("" : "+s"(Hb_r), "+s"(Wb_r), "+s"(nrx_r));
+        int Hb_r = Hb_k, Wb_r = Wb_k, nrx_r = nrx_k, nry_r = nry_k;      // kRwRebuildTid: ... and the reciprocals of the divisions by these
+        if (T::rebuild_tid) asm volatile("" : "+s"(Hb_r), "+s"(Wb_r), "+s"(nrx_r), "+s"(nry_r));
         const int Hb = Hb_r, Wb = Wb_r, nrx = nrx_r;
-        // BALANCED tiling: the grid's ceil(H / RTH) x ceil(W / RTW) regions share the rows / columns evenly (heights differ by at most
+        // BALANCED tiling: the grid's nry x nrx (at least ceil(H / RTH) x ceil(W / RTW)) regions share the rows / columns evenly (heights differ by at most
         // one row, none exceeds RTH: what the windows are sized for) instead of leaving a sliver at the bottom and right edges -- a
         // 100-row level is 4 x 25 or 5 x 20 rows, not 4 x 24 + 4
-        const int nry_b = (Hb + RTH - 1) / RTH, ry_b = reg / nrx, rx_b = reg - ry_b * nrx;
+        const int nry_b = nry_r, ry_b = reg / nrx, rx_b = reg - ry_b * nrx;
         const int y0b = (ry_b * Hb) / nry_b, y1b = ((ry_b + 1) * Hb) / nry_b;
         const int x0b = (rx_b * Wb) / nrx, x1b = ((rx_b + 1) * Wb) / nrx;
         // kRwRebuildTid: the per-level lane values are rebuilt per region from their wave-uniform copies (one select per level)
