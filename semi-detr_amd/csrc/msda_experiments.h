@@ -1,7 +1,8 @@
 // TEST / TUNING dispatch of the fp32 / D == 32 MSDA kernels: every kernel variant that was ever measured against the
 // defaults, selectable through semidetr_msda_set_variant (codes: DESIGN.md 2.3b).  Compiled ONLY into
 // libsemidetr_hip_exp.so (-DSEMIDETR_EXPERIMENTS=1); the product library has neither these kernels nor the variant state.
-// Included by msda.hip inside its anonymous namespace.
+// Included by msda.hip inside its anonymous namespace, after the product dispatch (msda_dispatch.h: pick_split, allow_big_lds, the grid
+// hints patch_grid_hint / region_grid_hint / region_grid_hint_loose, with the reason any bound >= 1 is correct; FwdStats: msda_fast.h).
 #pragma once      // msda.hip includes <atomic> at file scope (this header sits inside its anonymous namespace)
 
 std::atomic<int> g_fwd_variant_a{0}, g_bwd_variant_a{0};
@@ -16,10 +17,8 @@ int launch_rw(hipStream_t st, const float *grad_out, const float *value, const i
 {
     auto kern = &msda_rw_d32<IO, NT, RTH, RTW, H0, HC, KL, GATHER, DBG, TUNE>;
     if (int rc = allow_big_lds(kern, rw_lds_bytes<NT, RTH, RTW, H0, HC, KL, TUNE>(), "msda region-window kernel")) return rc;
-    // grid sizing hint: the finest level of a DETR pyramid holds ~3/4 of the pixels; a workgroup takes regions slot,
-    // slot + bound, ... so any bound >= 1 is correct (the level table lives in device memory)
     const int rpx = RTH * RTW;
-    const int bound = ((S * 3 / 4 + rpx - 1) / rpx) * 9 / 8 + 2 * KL;
+    const int bound = region_grid_hint(S, KL, rpx);
     const int64_t grid = (int64_t)N * bound * M;
     SEMIDETR_REQUIRE(grid < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda: grid too large");
     constexpr size_t lds = rw_lds_bytes<NT, RTH, RTW, H0, HC, KL, TUNE>();
@@ -132,7 +131,7 @@ int exp_launch_fast_forward(hipStream_t st, const float *value, const int64_t *s
     if constexpr (!IO::kSoftmax) {
         if (g_fwd_variant == 600 && pixels && L * P == 16 && P == kPT) {
             // LDS-window forward (msda_lw.h): 8 x 8 query patches, three workgroups per CU
-            const int bound = (S + 63) / 64 * 5 / 4 + 4 * L;
+            const int bound = patch_grid_hint(S, L, 64);
             SEMIDETR_REQUIRE((int64_t)N * bound * M < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_forward: grid too large");
             hipLaunchKernelGGL((msda_fwd_d32_lw<IO>), dim3((unsigned)(N * bound * M)), dim3(256), lw_lds_bytes(), st, value,
                                spatial_shapes, level_start, io, S, M, L, bound, out);
@@ -146,7 +145,7 @@ int exp_launch_fast_forward(hipStream_t st, const float *value, const int64_t *s
         // default at bs 4 -- taking the record phase off the consumers' critical path buys nothing, the vector-memory path is
         // limited by its misses in flight, not by how many waves feed it.
         const int per_cu = g_fwd_variant == 720 ? 4 : g_fwd_variant - 720;
-        const int bound = (S + 31) / 32 * 5 / 4 + 4 * L;
+        const int bound = patch_grid_hint(S, L, 32);
         const size_t wlds = (size_t)2 * 2 * 32 * (L * P + 1) * 16;
         SEMIDETR_REQUIRE(wlds <= 64 * 1024, SEMIDETR_E_BADARG, "msda_forward: the producer / consumer kernel needs L * P <= 63");
         const int hint = std::max(1, std::min(bound, (256 * per_cu + N * M - 1) / (N * M)));
@@ -169,7 +168,7 @@ int exp_launch_fast_forward(hipStream_t st, const float *value, const int64_t *s
         // 502 / 503: 4 patches per workgroup resident / control; 504 / 505: 2 patches
         const int grp = g_fwd_variant <= 501 ? 8 : (g_fwd_variant <= 503 ? 4 : 2);
         const int res_max = (g_fwd_variant & 1) ? 0 : kResRows;
-        const int G = ((S + 31) / 32 * 5 / 4 + 4 * L + grp - 1) / grp;      // grid sizing hint as for the patch kernel
+        const int G = (patch_grid_hint(S, L, 32) + grp - 1) / grp;      // grid sizing hint as for the patch kernel
         const size_t rlds = (size_t)(kResRows + 1) * 128 + (size_t)2 * 32 * (L * P + 1) * 32;
         SEMIDETR_REQUIRE(rlds <= 160 * 1024, SEMIDETR_E_BADARG, "msda_forward: too many samples per query for the resident-level kernel");
 #define LAUNCH_RES(GRP)                                                                                              \
@@ -193,8 +192,7 @@ int exp_launch_fast_forward(hipStream_t st, const float *value, const int64_t *s
     }
     if ((pixels && g_fwd_variant == 0) || g_fwd_variant == 408 || g_fwd_variant == 804 || g_fwd_variant == 216) {
         SEMIDETR_REQUIRE(pixels, SEMIDETR_E_BADARG, "msda_forward: patch tiling needs SEMIDETR_MSDA_QUERIES_ARE_PIXELS");
-        // grid sizing hint: about the number of 32-pixel patches of a usual pyramid (ragged edges included)
-        const int bound = (S + 31) / 32 * 5 / 4 + 4 * L;
+        const int bound = patch_grid_hint(S, L, 32);
         SEMIDETR_REQUIRE((int64_t)N * bound * M < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_forward: grid too large");
         const size_t lds = (size_t)32 * (L * P + 1) * 32;
         // measured at the 800x1333 encoder shape, bs 4, with the head rotation of tile_of_block: 4x8 246 us, 8x4 252,
@@ -480,7 +478,7 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
         }
         if (g_bwd_variant >= 6900 && g_bwd_variant <= 6919 && P == kPT && S < (1 << 23)) {
             // round 4: the whole encoder backward in ONE kernel after the fill (msda_bwd_enc_fused_d32); 6901 = instrumented
-            const int rbound = (S + 127) / 128 * 5 / 4 + 4 * L;
+            const int rbound = region_grid_hint_loose(S, L, 128);
             const int64_t rgrid = (int64_t)N * rbound * M;
             SEMIDETR_REQUIRE(rgrid < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_backward: grid too large");
             const size_t rlds = reg_lds_bytes<512, 208, 24, 32, 1>();
@@ -511,8 +509,8 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
         }
         if (g_bwd_variant == 697 && L * P == 16 && P == kPT && S < (1 << 23)) {
             // experiment: region scatter + gather in ONE launch, roles dealt out in groups of eight workgroups
-            const int rbound = (S + 127) / 128 * 5 / 4 + 4 * L;
-            const int gbound = (S + 31) / 32 * 5 / 4 + 4 * L;
+            const int rbound = region_grid_hint_loose(S, L, 128);
+            const int gbound = patch_grid_hint(S, L, 32);
             const int64_t sblocks = (int64_t)N * rbound * M, gblocks = (int64_t)N * gbound * M, gwgs = (gblocks + 1) / 2;
             const int64_t sgroups = (sblocks + 7) / 8, ggroups = (gwgs + 7) / 8;
             const int period = (int)std::max<int64_t>(2, (sgroups + ggroups) / sgroups);
@@ -540,8 +538,8 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
             // the launch carries the scatter's 77 KB of LDS, so a CU holds two workgroups in any mix and the gather, which
             // needs 16-24 waves per CU to stream, is left with 8.  (The same trick WINS for arbitrary query sets, where
             // the scatter's LDS is small enough for the halves to share CUs at full occupancy: msda_bwd_lvl_merged.)
-            const int tiles_bound = (S + 255) / 256 * 5 / 4 + 4 * L;
-            const int gbound = (S + 31) / 32 * 5 / 4 + 4 * L;
+            const int tiles_bound = patch_grid_hint(S, L, 256);
+            const int gbound = patch_grid_hint(S, L, 32);
             const int64_t sblocks = (int64_t)N * tiles_bound * M, gblocks = (int64_t)N * gbound * M;
             const int64_t gwgs = (gblocks + 1) / 2, total = sblocks + gwgs;
             const int period = (int)std::max<int64_t>(2, total / sblocks);         // every period-th workgroup scatters
@@ -577,7 +575,7 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
             const size_t glds = (size_t)32 * (L * P + 1) * 32 + 2 * kMaxLevels * sizeof(float);
             // DINO (L * P == 16): sample loop unrolled, results in registers, 8 x 4 query patches like the forward;
             // measured at the encoder shape, bs 4: generic strips 370 us, unrolled strips 346 us; 66 / 67 force them
-            const int gbound = (S + 31) / 32 * 5 / 4 + 4 * L;      // patch grid hint, see launch_fast_forward
+            const int gbound = patch_grid_hint(S, L, 32);
             if (L * P == 16 && g_bwd_variant == 6962)            // tuning: 8 loads in flight, 6 waves per SIMD
                 hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8), 6, 2>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
                                    st, grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound);
@@ -588,7 +586,7 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
                 hipLaunchKernelGGL((msda_bwd_gather_d32<IO, 16, patch_hw(4, 8), 4, 104>), dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds,
                                    st, grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound);
             else if (L * P == 16 && g_bwd_variant == 920) {       // four lanes per query, 8 x 8 patches (msda_bwd_gather4_d32)
-                const int gbound4 = (S + 63) / 64 * 5 / 4 + 4 * L;
+                const int gbound4 = patch_grid_hint(S, L, 64);
                 const size_t glds4 = (size_t)2 * 64 * (L * P + 1) * 16 + 2 * kMaxLevels * sizeof(float);
                 hipLaunchKernelGGL((msda_bwd_gather4_d32<IO, 16>), dim3((unsigned)((int64_t)N * gbound4 * M)), dim3(256), glds4, st,
                                    grad_out, value, spatial_shapes, level_start, io, S, M, L, Lq, P, gbound4,
@@ -623,7 +621,7 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
             // threads, two workgroups per CU); bs 1 248 -> 226 -> 216 us; row atomics 590 MB -> 358 MB (16 x 16).
             const bool small = g_bwd_variant != 690;              // 8 x 16 regions, 512 threads, two workgroups per CU
             const int rpx = g_bwd_variant == 692 || g_bwd_variant == 693 ? 64 : (small ? 128 : 256);
-            const int rbound = (S + rpx - 1) / rpx * 5 / 4 + 4 * L;
+            const int rbound = region_grid_hint_loose(S, L, rpx);
             const int64_t rgrid = (int64_t)N * rbound * M;
             SEMIDETR_REQUIRE(rgrid < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_backward: grid too large");
 #define LAUNCH_REG(NT_, Q_, RH_, RW_, WH_, WW_) LAUNCH_REGW(NT_, Q_, RH_, RW_, WH_, WW_, 4)
@@ -723,14 +721,13 @@ int exp_launch_fast_backward(hipStream_t st, const float *grad_out, const float 
             g_last_kernels = fill_in_gather ? "msda_bwd_gather_d32+msda_bwd_dest_d32" : "fillBufferAligned+msda_bwd_gather_d32+msda_bwd_dest_d32";
             return semidetr::launch_status("msda_bwd_dest_d32");
         }
-        // windowed (source-owned) kernel: patches are enumerated on the device (the level table lives in device
-        // memory); a workgroup takes patches slot, slot + tiles_bound, ... so any bound >= 1 is correct.
+        // windowed (source-owned) kernel: patches are enumerated on the device (grid size: patch_grid_hint).
         // measured at the 800x1333 encoder shape, bs 4: 8x16 patches 687 us / 784 MB of row atomics, 16x16 patches
         // 593 us / 604 MB (fewer halo rows per query); 64 forces the small patch
         SEMIDETR_REQUIRE(P == kPT, SEMIDETR_E_BADARG, "msda_backward: the windowed kernel needs num_point == 4");
         const bool big = g_bwd_variant != 64;
         const int patch = big ? 256 : 128;
-        const int tiles_bound = (S + patch - 1) / patch * 5 / 4 + 4 * L;
+        const int tiles_bound = patch_grid_hint(S, L, patch);
         const int64_t grid = (int64_t)N * tiles_bound * M;
         SEMIDETR_REQUIRE(grid < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_backward: grid too large");
         const size_t wlds = big ? win_lds_bytes<16, 16, 32, 32>() : win_lds_bytes<8, 16, 24, 32>();

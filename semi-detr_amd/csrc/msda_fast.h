@@ -1,7 +1,7 @@
 // Fast-path device code of the multi-scale deformable attention for gfx950 (fp32, 32 channels per head):
 // IO policies (reference op contract / fused MSDeformAttn prologue), forward, plain backward, and the
 // gather + owner-computes scatter pair used for encoder self-attention.  Included by msda.hip only (inside
-// its anonymous namespace); see msda.hip for the shared sample geometry and the host-side dispatch.
+// its anonymous namespace); see msda_geom.h for the shared sample geometry and msda_dispatch.h for the host-side dispatch.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
@@ -613,7 +613,7 @@ __device__ __forceinline__ int patch_query(const Patch &p, int r)      // r-th q
 
 // ---------------------------------------------------------------------------------------------
 // How far the samples of an encoder self-attention launch reach -- the statistic the dispatcher picks the forward kernel by
-// (msda.hip: launch_fast_forward).  The region-window kernel (msda_rw.h) serves the coarse levels' corners from LDS windows placed
+// (msda_policy.h: fwd_adapt_next, for msda_dispatch.h: launch_fast_forward).  The region-window kernel (msda_rw.h) serves the coarse levels' corners from LDS windows placed
 // +- 5 px (five levels: +- 4 px) around a region: ~30 % faster than the patch kernel at sigma <= 2 px (162 against 234 us at bs 4 inside
 // the step), level with it at sigma ~5.5 px = ~70 % of the samples further than 4 px away, slower beyond (the single source of
 // these numbers: profiles/r04_region_window_dispatch.txt).  Both kernels therefore count, in a few sampled workgroups,

@@ -24,12 +24,10 @@
 //   * a sample whose footprint leaves its window is handled by the WHOLE wave afterwards (rare while the offsets stay near the
 //     queries): lane -> (corner, 8-byte piece) loads the four rows coalesced, multiplies with the query's grad_out piece, a DPP row
 //     sum per corner, the owner takes the four dots.  Any input is correct; locality only decides speed (the dispatcher takes the
-//     patch gather when the slot's forward policy says the samples are far, msda.hip).
+//     patch gather when the slot's forward policy says the samples are far, msda_policy.h slot_samples_are_near).
+// Its knobs (SEMIDETR_GW_*, among them the dot loop's SEMIDETR_GW_SB) are msda_tuning.h's; the product's instantiations: msda_dispatch.h GwProduct.
 #pragma once
 
-#ifndef SEMIDETR_GW_SB
-#define SEMIDETR_GW_SB 1            // dot-loop steps (five ds_read_b128 each) between scheduling barriers
-#endif
 constexpr int kGwQList = 512;       // queries of a region kept as a list in LDS (a region of a halving pyramid has ~340; larger ones compute them)
 // far samples a wave hands to its rows at a time (32-byte entries in LDS; four rows take one entry each per trip: five levels, whose windows
 // leave less room, hand over one trip's worth)

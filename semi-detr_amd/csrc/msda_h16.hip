@@ -444,7 +444,7 @@ bool fast_ok(const void *a, const void *b, const void *c, int S, int M, int D, i
            (int64_t)S * M * kD * 2 < (int64_t)0xFFFFF000u;
 }
 
-int pick_split(int N, int Lq, int M)      // as the fp32 forward (msda.hip pick_split): small query sets spread a row over more lanes
+int pick_split(int N, int Lq, int M)      // as the fp32 forward (msda_dispatch.h pick_split): small query sets spread a row over more lanes
 {
     const int64_t wg32 = (int64_t)N * M * ((Lq + 31) / 32);
     return wg32 >= 2048 ? 1 : (wg32 >= 1024 ? 2 : 4);

@@ -22,7 +22,7 @@
 // NT threads; kRegQ queries per pass; region = RTH x RTW pixels of the finest level; WH x WW window per sampling level.
 // Product (round 5): <512, 256, 8, 24, 24, 40> -- 8 x 24 regions, two workgroups per CU (74.5 KB of LDS each; the phases of one hide the
 // barriers of the other).  Rounds 2-4 ran <512, 208 / 176, 8, 16, 24, 32> at two / three per CU: the optimum while the walk's compute
-// was a co-limit; with the cheap flush path the atomic unit binds and fewer flushed rows win (msda.hip SEMIDETR_SCATTER_*).
+// was a co-limit; with the cheap flush path the atomic unit binds and fewer flushed rows win (msda_tuning.h SEMIDETR_SCATTER_*; the instantiation: msda_dispatch.h ScatterProduct).
 template <int NT, int kRegQ, int WH, int WW, int FUSE = 0>
 constexpr size_t reg_lds_bytes()
 {
@@ -99,7 +99,7 @@ __device__ __forceinline__ void reg_scatter_body(
         if (h * w > Hb * Wb) { lb = l; Hb = h; Wb = w; }
     }
     (void)lb;
-    // grid_ry x grid_rx (both 0: none): the region grid the host chose for this launch from its copy of the level table (msda.hip
+    // grid_ry x grid_rx (both 0: none): the region grid the host chose for this launch from its copy of the level table (msda_grid.h
     // region_grid_choice), tiled EVENLY like the window kernels' and never coarser than ceil(H / RTH) x ceil(W / RTW), which the windows are
     // sized for.  None: that grid in steps of RTH x RTW, the remainder at the bottom and right edges.
     const bool even = (grid_ry | grid_rx) != 0;
@@ -520,7 +520,7 @@ __device__ __forceinline__ void reg_scatter_body(
                         if constexpr (kPixKey) {
                             // byte offset of the lane's first channel from the window's first pixel: one 24-bit multiply-add; the two
                             // half-line atomics take the scalar base (the instructions fp_atomic_add compiles to, saddr form).
-                            // 16-bit key x row pitch must stay below 2^32: M * 128 <= 4096 on every fast-path launch (heads_ok, msda.hip;
+                            // 16-bit key x row pitch must stay below 2^32: M * 128 <= 4096 on every fast-path launch (heads_ok, msda_dispatch.h;
                             // launch_fast_backward repeats the bound next to this kernel's launch -- ADVICE r05).  gfx9 encodings.
 #if !defined(__gfx950__) && !defined(__gfx942__) && !defined(__gfx90a__) && defined(__HIP_DEVICE_COMPILE__)
 #error "msda_region.h: the flush path is written in gfx9 (CDNA) assembly"
@@ -744,9 +744,7 @@ __global__ __launch_bounds__(NT, WPE) void msda_bwd_scatter_d32_reg(
 {
     io.same_dims(S, M, L);
     extern __shared__ float4 smem[];
-#ifndef SEMIDETR_SCATTER_AID
-#define SEMIDETR_SCATTER_AID 0      // tuning builds (tools/ab_build.sh -DSEMIDETR_SCATTER_AID=...): timing aids of the walk, results wrong
-#endif
+    // (SEMIDETR_SCATTER_AID, msda_tuning.h: 0; tuning builds: timing aids of the walk, results wrong)
     reg_scatter_body<IO, NT, kRegQ, RTH, RTW, WH, WW, DBG, WU, 0, SEMIDETR_SCATTER_AID>((int)blockIdx.x, smem, gout, shapes, starts, io, S, M, L,
                                                           regions_bound, gvalue, nullptr, grid_ry, grid_rx);
 }

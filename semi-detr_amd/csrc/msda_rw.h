@@ -6,7 +6,7 @@
 // launch_fast_forward picks while most samples stay within a few pixels of their queries (FwdStats); the other
 // configurations and the gather half are reachable from the experiments library only.  A configuration is the template argument TUNE =
 // rw_tune(named flags, samples between scheduling barriers, pre-issued out-of-window samples), defined and decoded below (kRw..., RwTune)
-// and nowhere else; the product's are msda.hip's SEMIDETR_RW_TUNE...; tools/rw_regs.sh compiles one configuration in seconds and prints
+// and nowhere else; the product's are RwProduct's (msda_dispatch.h) from msda_tuning.h's SEMIDETR_RW_TUNE...; tools/rw_regs.sh compiles one configuration in seconds and prints
 // its VGPRs and spills.
 //
 // Why.  The patch kernels (msda_fwd_d32<1,4,408>, msda_bwd_gather_d32) pull every corner row through the vector-memory
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : 2)) void msda_rw_d32(  
     // the region grid lives on level 0 (the finest level of a DETR pyramid; any order is correct, the windows are sized
     // for this one)
     const int Hb = Hs[0], Wb = Ws[0];
-    // grid_ry x grid_rx: the region grid the host chose for this launch from its copy of the level table (msda.hip region_grid_choice); 0, or
+    // grid_ry x grid_rx: the region grid the host chose for this launch from its copy of the level table (msda_grid.h region_grid_choice); 0, or
     // anything coarser than the windows are sized for: ceil(H / RTH) x ceil(W / RTW).  Finer grids only make the regions smaller.
     const int nry = max(grid_ry, (Hb + RTH - 1) / RTH), nrx = max(grid_rx, (Wb + RTW - 1) / RTW);
 

@@ -23,10 +23,8 @@
 //   an LDS buffer serialised the row atomics behind the walk: 331 us with the entry loop removed.)
 // Samples whose cell lies outside the window (or on its last row / column) scatter their corners one by one, like the region
 // scatter's misses: any sampling pattern is correct.  Regions with more than Q queries are processed in passes.
+// Its knobs (SEMIDETR_SW_*, the timing aids SEMIDETR_SW_DBG among them): msda_tuning.h.
 #pragma once
-#ifndef SEMIDETR_SW_DBG
-#define SEMIDETR_SW_DBG 0      // timing aids (tuning builds, results wrong): 1 no entry loop, 2 no flush, 4 no misses, 8 no walk at all
-#endif
 
 template <int NT, int Q, int WH, int WW>
 constexpr size_t sw_lds_bytes()

@@ -1,5 +1,5 @@
 """GPU: the run-time region grid of the three encoder window kernels (msda_rw_d32 forward, msda_gw_d32 gather,
-msda_bwd_scatter_d32_reg scatter; csrc/msda.hip region_grid_choice) against the fp64 reference with its per-element bounds
+msda_bwd_scatter_d32_reg scatter; csrc/msda_grid.h region_grid_choice) against the fp64 reference with its per-element bounds
 (tests/msda_ref64.py).  Every grid a launch may be given -- the coarsest, uneven tiles, one-row regions, regions without a level-0
 pixel -- must produce every query exactly once: the kernels run through the C ABI into buffers filled with NaN beforehand, so a query
 no region took stays NaN, and a query two regions of the scatter took doubles its grad_value rows and leaves the bound.  (The forward

@@ -5,7 +5,7 @@
   * the bound can be met by honest fp32 arithmetic: the fp32 oracle passes it on every small configuration the GPU module uses;
   * it is tight enough to catch what a kernel rewrite might slip in: value read as fp16 / bf16, weights rounded to fp16, the
     smallest sample dropped, locations shifted by 1e-4 px, 1e-5 noise on the attention -- each fails it;
-  * the GPU module's route table lists every kernel route the product dispatcher (semi-detr_amd/csrc/msda.hip) can report.
+  * the GPU module's route table lists every kernel route the product dispatcher (semi-detr_amd/csrc/msda.hip, msda_dispatch.h) can report.
 """
 import os
 import re
@@ -162,9 +162,9 @@ def test_mutants_break_the_bound(mutant):
 # ---- the route table
 
 def product_routes():
-    """Every string the product build of msda.hip can assign to g_last_kernels ("" and the SEMIDETR_SCATTER_SW knob's msda_sw_d32
-    routes excluded)."""
-    src = open(os.path.join(ROOT, "semi-detr_amd", "csrc", "msda.hip")).read()
+    """Every string the product build of msda.hip (with its product dispatch, msda_dispatch.h) can assign to g_last_kernels ("" and
+    the SEMIDETR_SCATTER_SW knob's msda_sw_d32 routes excluded)."""
+    src = "".join(open(os.path.join(ROOT, "semi-detr_amd", "csrc", name)).read() for name in ("msda.hip", "msda_dispatch.h"))
     found = set()
     for stmt in re.findall(r"g_last_kernels\s*=\s*([^;]*);", src):
         found.update(re.findall(r'"([^"]*)"', stmt))

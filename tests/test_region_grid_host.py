@@ -1,4 +1,4 @@
-"""CPU: the region grids the library chooses per launch for the three encoder window kernels (csrc/msda.hip region_grid_choice),
+"""CPU: the region grids the library chooses per launch for the three encoder window kernels (csrc/msda_grid.h region_grid_choice),
 through semidetr_msda_region_grid_query -- no GPU.  The kernels' query -> region map (msda_rw.h / msda_gw.h / msda_region.h: even
 tiling of the finest level, a level-l pixel belongs to the region its centre maps into) is restated here from the level table and
 must cover every pixel of every level exactly once for every grid a test pins."""
@@ -16,7 +16,7 @@ KERNELS = ("forward", "gather", "scatter")
 
 
 def largest_region(kernel, levels):
-    """(RTH, RTW) the kernel's windows are sized for (csrc/msda.hip: SEMIDETR_RW_RTH / _RTH5, SEMIDETR_GW_RTH / _RTH5, SEMIDETR_SCATTER_RTH / _RTW)"""
+    """(RTH, RTW) the kernel's windows are sized for (csrc/msda_tuning.h: SEMIDETR_RW_RTH / _RTH5, SEMIDETR_GW_RTH / _RTH5, SEMIDETR_SCATTER_RTH / _RTW)"""
     five = len(levels) == 5
     return {"forward": (24 if five else 25, 16), "gather": (13 if five else 15, 16), "scatter": (8, 24)}[kernel]
 
