@@ -15,6 +15,14 @@ only where they are not), so the decoder's ``(nq, bs, 256)`` views and transpose
 place, adopting their ``Parameter`` objects.  ``encoder_layer_forward``, ``encoder_forward`` and ``decoder_layer_forward*``
 re-state the reference's layer control flow with the fused epilogue; ``registry.bind_layer_epilogues()`` binds them.
 
+Dtypes.  ``x``, ``residual``, ``pos``, ``weight`` and ``bias`` may each be fp32, fp16 or bf16, in any mixture; every one is
+up-cast exactly, the arithmetic is fp32, and each result is rounded once on its way out (``q`` from the unrounded ``y``).  What
+comes back has the dtype stock torch gives ``F.layer_norm(x + residual, ...)`` and ``... + pos`` in the caller's autocast state:
+under enabled CUDA autocast ``y`` and ``q`` are fp32 whatever came in (``layer_norm`` is on autocast's fp32 list), so the fp32
+residual stream of a layer stays fp32 although the branch added to it is 16-bit; outside autocast ``y`` has the promoted type of
+``x`` and ``residual`` and ``q`` that of ``y`` and ``pos`` (a ``.half()`` module: all fp16; the parameters' dtype plays no part).
+Every gradient has the dtype of the tensor it belongs to.
+
 Not built: widths other than 256, 16-bit I/O inside the kernel (16-bit inputs are computed in fp32),
 ``normalize_before``, fusing ``norm3`` with the decoder's final ``norm``, the bias of ``linear2`` / ``out_proj``.
 """
@@ -61,6 +69,20 @@ def _check(x, residual, weight, bias, pos):
             raise RuntimeError(f"add_layer_norm: {what} must live on the GPU (no CPU fallback)")
     if x.numel() // DIM >= 2 ** 31:
         raise ValueError("add_layer_norm: too many rows (rows < 2^31)")
+
+
+def _result_dtypes(x, residual, pos):
+    """The dtypes of ``y`` and ``q`` from those of ``x``, ``residual`` and ``pos`` (``None`` where absent): what stock torch
+    returns for ``layer_norm(x + residual)`` and for that ``+ pos`` in the caller's autocast state.  The sum has the promoted
+    type of its operands; under enabled CUDA autocast ``layer_norm`` is on the fp32 list, so a 16-bit sum still gives an
+    fp32 ``y``; ``q`` has the promoted type of ``y`` and ``pos``.  Both are computed in fp32 from the up-cast operands and
+    rounded once, ``q`` from the unrounded ``y``."""
+    if x == torch.float32 and residual in (None, x) and pos in (None, x):
+        return x, x
+    y = x if residual is None else torch.promote_types(x, residual)
+    if y in (torch.float16, torch.bfloat16) and torch.is_autocast_enabled("cuda"):
+        y = torch.float32
+    return y, y if pos is None else torch.promote_types(y, pos)
 
 
 def add_layer_norm_forward(x, residual, weight, bias, eps=1e-5, pos=None):
@@ -125,8 +147,9 @@ class AddLayerNormFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.dtypes = (x.dtype, None if residual is None else residual.dtype, weight.dtype, bias.dtype,
                       None if pos is None else pos.dtype)
-        y = _lib.cast(y, x.dtype)
-        return y if pos is None else (y, _lib.cast(q, x.dtype))
+        y_dtype, q_dtype = _result_dtypes(*ctx.dtypes[:2], ctx.dtypes[4])
+        y16 = _lib.cast(y, y_dtype)
+        return y16 if pos is None else (y16, _lib.cast(q, q_dtype))
 
     @staticmethod
     @once_differentiable

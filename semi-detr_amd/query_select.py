@@ -12,6 +12,14 @@ Selection order.  ``torch.topk`` leaves the order among equal keys open, and eve
 zeroed ``output_memory`` row, hence bit-identical logits.  Here the k tokens come sorted by (key descending, token index
 ascending): a total order, so the choice among tied tokens is the lowest indices, run after run.  NaN ranks above +inf.
 
+Dtypes.  Every floating operand may be fp32, fp16 or bf16, each on its own: under autocast ``fc_enc_cls`` hands
+``select_queries`` 16-bit logits next to fp32 coordinates, proposals and memory; a ``.half()`` model hands over 16-bit memory.
+16-bit operands are up-cast exactly and the kernels run in fp32, so the selected tokens are the first k of the total order on
+the keys as given.  The results have the dtypes the reference's op sequence gives: ``output_memory`` that of ``memory``, the
+proposals fp32, ``refpoint_embed_undetach`` and ``ref_enc`` that of ``enc_outputs_coord``, ``init_box_proposal`` that of
+``output_proposals``, ``tgt_undetach`` that of ``output_memory``; copies are bitwise, a sigmoid that leaves in 16 bits is rounded
+once.  Gradients have the dtype of the tensor they belong to.
+
 ``forward_with_query`` (transformer.py:1409-1481) has no two-stage block -- it takes its queries from the caller -- so only
 ``forward`` has a use for ``two_stage_queries``.
 """
@@ -30,8 +38,11 @@ def _require(t, what):
 
 
 def _f32(t, what):
+    """``t`` as the kernels read it: detached, contiguous, fp32.  fp16 and bf16 are up-cast (exact); other dtypes are refused."""
     if t.dtype != torch.float32:
-        raise TypeError(f"query_select: {what} must be float32, got {t.dtype}")
+        if t.dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError(f"query_select: {what} must be float32, float16 or bfloat16, got {t.dtype}")
+        return t.detach().float().contiguous()
     return t if t.is_contiguous() and not t.requires_grad else t.detach().contiguous()
 
 
@@ -74,7 +85,8 @@ class _ProposalsFn(torch.autograd.Function):
         ctx.save_for_backward(valid)
         ctx.mark_non_differentiable(prop)
         ctx.set_materialize_grads(False)
-        return out, prop
+        ctx.dtype = memory.dtype
+        return _lib.cast(out, memory.dtype), prop
 
     @staticmethod
     def backward(ctx, g_out, _g_prop):
@@ -85,7 +97,7 @@ class _ProposalsFn(torch.autograd.Function):
         N, S, D = g.shape
         gm = torch.empty_like(g)
         _lib.call("semidetr_qsel_proposals_backward_f32", g.device, g, valid, N, S, D, gm)
-        return gm, None, None
+        return _lib.cast(gm, ctx.dtype), None, None
 
 
 def gen_encoder_output_proposals(memory, memory_padding_mask, spatial_shapes, learnedwh=None):
@@ -118,7 +130,10 @@ class _SelectFn(torch.autograd.Function):
         _lib.calls(dev, ("semidetr_qsel_topk_f32", lg, N, S, C, k, ws, ws_bytes, idx, inv),
                    ("semidetr_qsel_gather_f32", idx, cd, pr, mem, N, S, k, D, ref, init_box, tgt, ref_enc))
         ctx.sizes = (N, S, k, D)
-        ctx.save_for_backward(inv, ref_enc)
+        ctx.dtypes = (coord.dtype, memory.dtype)
+        ctx.save_for_backward(inv, ref_enc)                        # the fp32 sigmoid, before any rounding on the way out
+        ref, ref_enc = _lib.cast(ref, coord.dtype), _lib.cast(ref_enc, coord.dtype)
+        init_box, tgt = _lib.cast(init_box, proposals.dtype), _lib.cast(tgt, memory.dtype)
         ctx.mark_non_differentiable(idx, init_box)
         ctx.set_materialize_grads(False)
         return idx, ref, init_box, tgt, ref_enc
@@ -136,7 +151,7 @@ class _SelectFn(torch.autograd.Function):
         gc = torch.empty((N, S, 4), dtype=torch.float32, device=dev) if want_c else None
         gm = torch.empty((N, S, D), dtype=torch.float32, device=dev) if want_m else None
         _lib.call("semidetr_qsel_gather_backward_f32", dev, inv, g_ref, g_tgt, g_enc, ref_enc, N, S, k, D, gc, gm)
-        return None, gc, None, gm, None
+        return None, _lib.cast(gc, ctx.dtypes[0]), None, _lib.cast(gm, ctx.dtypes[1]), None
 
 
 def select_queries(enc_outputs_class, enc_outputs_coord, output_proposals, output_memory, num_queries):

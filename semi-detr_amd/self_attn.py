@@ -13,6 +13,11 @@ tiles are skipped.  A row with every key blocked is NaN, as in torch.
 reference ``state_dict`` loads with ``strict=True``); the two projections stay GEMMs.  ``convert_self_attention(module)``
 replaces the qualifying ``nn.MultiheadAttention`` children of a built model in place, adopting their ``Parameter`` objects.
 
+Dtypes.  ``q``, ``k`` and ``v`` may be fp32, fp16 or bf16; 16-bit operands are up-cast exactly, the arithmetic is fp32, and
+``out`` comes back in the dtype of ``q`` (of the packed ``[q | k]`` buffer), rounded once; each gradient has the dtype of its
+operand.  Under autocast the module's projections are 16-bit GEMMs, so the core receives and returns 16-bit tensors and the module
+returns what ``nn.MultiheadAttention`` returns there: a 16-bit output, fp32 gradients for fp32 inputs and parameters.
+
 Not built: float and 3-D masks, ``key_padding_mask``, attention dropout, head dimensions other than 32,
 16-bit inputs (they are computed in fp32) and the head-averaged attention weights.
 """

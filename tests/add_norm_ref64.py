@@ -150,16 +150,30 @@ def within(name, got, a):
                            f"(off by {abs(got[i] - a[0][i]):.3e}; {int(bad.sum())} of {bad.size} elements outside)")
 
 
-def check_add_norm(case, got, name, ref=None):
+def widen16(a, dtype):
+    """The pair of a result that leaves in a 16-bit type (``'fp16'`` / ``'bf16'``): the fp32 bound widened by the one output
+    rounding, B + u16 (|ref| + B) + s16 (tests/msda_h16_ref.py).  ``None``: the pair as it is.  The inputs of such a case are
+    16-bit numbers held in fp32 (exact), so the statement itself is unchanged."""
+    if dtype is None:
+        return a
+    from msda_h16_ref import widen16 as widen
+    with np.errstate(invalid="ignore"):
+        return a[0], widen(a[1], a[0], dtype)
+
+
+def check_add_norm(case, got, name, ref=None, dtypes=None):
     """got: dict with any of y, q, mean, rstd, dx, dweight, dbias -> {output: worst |err| / bound}; raises Inadmissible naming
-    the case, the output and the index.  An output the statement has and ``got`` lacks is not judged."""
+    the case, the output and the index.  An output the statement has and ``got`` lacks is not judged.  ``dtypes``: {output:
+    'fp16' | 'bf16'} for the outputs that were rounded once into that type (``widen16``); every other output keeps the fp32
+    bound."""
     ref = ref64(case) if ref is None else ref
     rep = {}
     for k, v in got.items():
         if k not in ref:
             raise Inadmissible(f"{name}: {k} given but the case has no statement for it")
-        within(f"{name}: {k}", v, ref[k])
-        rep[k] = ratio(v, ref[k])
+        a = widen16(ref[k], (dtypes or {}).get(k))
+        within(f"{name}: {k}", v, a)
+        rep[k] = ratio(v, a)
     return rep
 
 

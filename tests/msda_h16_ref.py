@@ -43,6 +43,13 @@ def round16(x, dtype):
     return t.to(torch_dtype(dtype)).to(torch.float32).numpy()
 
 
+def widen16(b32, val, dtype):
+    """The fp32 bound ``b32`` of a result whose reference value is ``val``, widened by the one rounding into the 16-bit type
+    (module docstring): B32 + u16 (|ref| + B32) + s16.  Shared by every judge of a 16-bit result (add_norm_ref64,
+    self_attn_ref64, query_select_ref64)."""
+    return b32 + U16[dtype] * (np.abs(val) + b32) + S16[dtype]
+
+
 class Bounded16:
     """A msda_ref64.Bounded result of a 16-bit output: the fp32 bound widened by the one rounding."""
 
@@ -50,8 +57,7 @@ class Bounded16:
         self.b32, self.dtype, self.val, self.skip = b32, dtype, b32.val, b32.skip
 
     def bound(self):
-        b = self.b32.bound(np.float32)
-        return b + U16[self.dtype] * (np.abs(self.val) + b) + S16[self.dtype]
+        return widen16(self.b32.bound(np.float32), self.val, self.dtype)
 
     def reach(self):
         """|ref| + B32: what the value before the rounding can be at most (the fp16 range condition)."""

@@ -143,6 +143,15 @@ def gather_backward(indices, S, ref_enc, g_ref, g_tgt, g_enc):
     return gc, bound, gm
 
 
+def widen16(bound, value, dtype):
+    """``bound`` of a result with the float64 value ``value`` that leaves in a 16-bit type (``'fp16'`` / ``'bf16'``), widened by
+    that one rounding: B + u16 (|ref| + B) + s16 (tests/msda_h16_ref.py).  ``None``: unchanged."""
+    if dtype is None:
+        return bound
+    from msda_h16_ref import widen16 as widen
+    return widen(np.asarray(bound, np.float64), np.asarray(value, np.float64), dtype)
+
+
 def unique_key_slots(keys, indices):
     """(N, k) bool: the slot's key occurs once in its image (its token is then decided by the keys alone)."""
     out = np.zeros(indices.shape, bool)

@@ -138,13 +138,18 @@ def ref64(problem, grads=True):
     return res
 
 
-def judge_self_attn(problem, got, ref=None):
+def judge_self_attn(problem, got, ref=None, dtype16=None):
     """-> {tensor: largest |got - ref| / bound over its elements (inf where a NaN is on one side only)} for the tensors in
-    ``got`` (``out``, ``dq``, ``dk``, ``dv``), no element left out."""
+    ``got`` (``out``, ``dq``, ``dk``, ``dv``), no element left out.  ``dtype16`` (``'fp16'`` / ``'bf16'``): the results were
+    rounded once into that type, and every bound is widened to B + u16 (|ref| + B) + s16 (tests/msda_h16_ref.py)."""
     ref = ref or ref64(problem, grads=any(n in got for n in ("dq", "dk", "dv")))
     rep = {"rel": ref["rel"]}
     for name, val in got.items():
         want, bound = ref[name], ref["b_" + name]
+        if dtype16 is not None:
+            from msda_h16_ref import widen16
+            with np.errstate(invalid="ignore"):
+                bound = widen16(bound, want, dtype16)
         val = np.asarray(val, np.float64)
         assert val.shape == want.shape, (name, val.shape, want.shape)
         nan_w, nan_g = np.isnan(want), np.isnan(val)
@@ -157,10 +162,10 @@ def judge_self_attn(problem, got, ref=None):
     return rep
 
 
-def check_self_attn(problem, got, name="", ref=None):
+def check_self_attn(problem, got, name="", ref=None, dtype16=None):
     """Every element of every tensor in ``got`` within its bound of the float64 statement (a fully blocked row: NaN on both
     sides).  Returns the report of ``judge_self_attn``."""
-    rep = judge_self_attn(problem, got, ref)
+    rep = judge_self_attn(problem, got, ref, dtype16)
     assert rep["rel"] < 1e-2, f"{name}: a relative error term of {rep['rel']:.3g}: the first-order bounds do not apply"
     bad = {k_: v_ for k_, v_ in rep.items() if k_ != "rel" and not v_ <= 1.0}
     assert not bad, f"{name}: outside the bound (error / bound): {bad}"
