@@ -885,6 +885,60 @@ int semidetr_add_norm_forward_f32(void *stream, const semidetr_add_norm *params 
 int semidetr_add_norm_backward_f32(void *stream, const semidetr_add_norm *params /* host */, void *workspace,
                                    size_t workspace_bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * The same op on rows of mixed element types (ABI 7, additive): what torch.autocast and .half() modules hand the epilogue,
+ * without fp32 copies of the operands and without cast passes over the results.
+ *
+ * Every row operand (x, residual, pos, gy, gq) and every row result (y, q, grad_x, grad_residual, grad_pos) carries its own
+ * element type in the `<name>_type` field: SEMIDETR_ROW_F32, SEMIDETR_ROW_FP16 (IEEE binary16) or SEMIDETR_ROW_BF16
+ * (bfloat16), in any mixture; the types of the results do not depend on those of the operands.  The type field of a NULL
+ * pointer is not read.  weight, bias, mean, rstd, grad_weight, grad_bias and the workspace are fp32.
+ * Contract: the arithmetic, the grid, the row -> wave map, the slots and the order of every sum are those of the fp32 entry
+ * points above.  A 16-bit operand is up-cast exactly when it is loaded; a 16-bit result is rounded ONCE, to nearest even, from
+ * the unrounded fp32 value when it is stored (fp16 overflows to inf, as the conversion does); q is rounded from the unrounded
+ * y + pos, never from a rounded y.  So every result is bit for bit the result of the fp32 entry point on the up-cast operands,
+ * converted once; mean, rstd, grad_weight and grad_bias are those of the fp32 entry point.
+ * Layout: as above -- operands through the strides of their two leading dimensions in ELEMENTS, last stride 1, results
+ * contiguous (rows0, rows1, dim).  Alignment per type: an fp32 row starts 16-byte aligned (base 16-byte aligned, strides
+ * non-negative multiples of 4); a 16-bit row starts 8-byte aligned (base 8-byte aligned, strides non-negative multiples of 4), so
+ * a 16-bit slice whose rows sit at 8 but not 16 bytes is read in place.  A result is 16-byte (fp32) or 8-byte (16-bit) aligned;
+ * weight, bias and the workspace 16-byte.
+ *
+ * semidetr_add_norm_forward_mixed  -- one launch.  Reads x, residual (may be NULL), pos (NULL exactly where q is NULL), weight,
+ *   bias.  Writes y, q, mean, rstd.  Uses no workspace (NULL, 0 is accepted).
+ * semidetr_add_norm_backward_mixed -- two launches (one where grad_weight and grad_bias are both NULL).  Reads x, residual, gy,
+ *   gq (either may be NULL, not both), weight, mean, rstd.  From the one fp32 dx = grad_x of the fp32 entry point it writes
+ *     grad_x         in grad_x_type          (the gradient of x),
+ *     grad_residual  in grad_residual_type   (the gradient of residual where its type differs from x's; needs residual);
+ *   either may be NULL, not both.  grad_pos (may be NULL; needs gq) receives gq converted to grad_pos_type: the gradient of
+ *   pos where its type differs from gq's.  grad_weight and grad_bias (each may be NULL) as above; bias, y, q and pos are not read.
+ * workspace: semidetr_add_norm_workspace_bytes(rows0 * rows1), as above.
+ * Every argument is checked on the host before anything is launched: an unknown type code, a misaligned row, q without pos (or
+ * pos without q), no grad_x and no grad_residual, grad_residual without residual, grad_pos without gq and the checks of the
+ * fp32 entry points are SEMIDETR_E_BADARG; rows0 * rows1 >= 2^31 is SEMIDETR_E_TOOLARGE.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_ROW_F32 0
+#define SEMIDETR_ROW_FP16 1
+#define SEMIDETR_ROW_BF16 2
+typedef struct semidetr_add_norm_mixed {
+    int rows0, rows1, dim;
+    float eps;
+    const void *x, *residual, *pos;                       /* residual, pos: NULL = absent */
+    const void *gy, *gq;                                  /* backward only */
+    int64_t x_stride[2], residual_stride[2], pos_stride[2], gy_stride[2], gq_stride[2];   /* in elements */
+    const float *weight, *bias;                           /* (dim) */
+    void *y, *q;                                          /* forward: written */
+    float *mean, *rstd;                                   /* forward: written; backward: read */
+    void *grad_x, *grad_residual, *grad_pos;              /* backward: written */
+    float *grad_weight, *grad_bias;                       /* backward: written */
+    int x_type, residual_type, pos_type, gy_type, gq_type;                        /* SEMIDETR_ROW_* of the operands */
+    int y_type, q_type, grad_x_type, grad_residual_type, grad_pos_type;           /* SEMIDETR_ROW_* of the results */
+} semidetr_add_norm_mixed;
+int semidetr_add_norm_forward_mixed(void *stream, const semidetr_add_norm_mixed *params /* host */, void *workspace,
+                                    size_t workspace_bytes);
+int semidetr_add_norm_backward_mixed(void *stream, const semidetr_add_norm_mixed *params /* host */, void *workspace,
+                                     size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

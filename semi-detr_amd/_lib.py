@@ -35,6 +35,8 @@ CONSTANTS = {
     "SEMIDETR_DET_MAX_K": 2048,
     "SEMIDETR_CONSIS_MAX_LAYERS": 16,
 }
+# the element type codes of semidetr_add_norm_mixed's rows (tests/test_add_norm_mixed_ref.py reads them back from the header)
+ROW_TYPES = {"SEMIDETR_ROW_F32": 0, "SEMIDETR_ROW_FP16": 1, "SEMIDETR_ROW_BF16": 2}
 _DN_IMAGES, _CONSIS_LAYERS = CONSTANTS["SEMIDETR_DN_MAX_IMAGES"], CONSTANTS["SEMIDETR_CONSIS_MAX_LAYERS"]
 _STRIDE2 = c_int64 * 2                # the strides of a tensor's two leading dimensions, in elements
 
@@ -99,10 +101,19 @@ class AddNorm(ctypes.Structure):
                 + _f(c_void_p, "weight bias y q mean rstd grad_x grad_weight grad_bias"))
 
 
+class AddNormMixed(ctypes.Structure):
+    _fields_ = (_f(c_int, "rows0 rows1 dim") + _f(c_float, "eps") + _f(c_void_p, "x residual pos gy gq")
+                + _f(_STRIDE2, "x_stride residual_stride pos_stride gy_stride gq_stride")
+                + _f(c_void_p, "weight bias y q mean rstd grad_x grad_residual grad_pos grad_weight grad_bias")
+                + _f(c_int, "x_type residual_type pos_type gy_type gq_type y_type q_type grad_x_type grad_residual_type "
+                            "grad_pos_type"))
+
+
 # C struct -> mirror, in the header's order
 STRUCTS = {"semidetr_cost_params": CostParams, "semidetr_set_loss_segment": SetLossSegment, "semidetr_dn_layout": DnLayout,
            "semidetr_dn_build": DnBuild, "semidetr_dn_consistency": DnConsistency, "semidetr_consis_layer": ConsisLayer,
-           "semidetr_consis_loss": ConsisLoss, "semidetr_self_attn": SelfAttn, "semidetr_add_norm": AddNorm}
+           "semidetr_consis_loss": ConsisLoss, "semidetr_self_attn": SelfAttn, "semidetr_add_norm": AddNorm,
+           "semidetr_add_norm_mixed": AddNormMixed}
 _SEGS, _WORK = POINTER(SetLossSegment), [c_void_p, c_size_t]        # a segment table; the (workspace, workspace_bytes) pair
 
 _MSDA_FWD = [c_void_p] * 6 + [c_int] * 7 + [c_void_p]
@@ -187,6 +198,8 @@ SIGNATURES = {
     "semidetr_add_norm_workspace_bytes": (c_size_t, [c_int64]),
     "semidetr_add_norm_forward_f32": (c_int, [c_void_p, POINTER(AddNorm)] + _WORK),
     "semidetr_add_norm_backward_f32": (c_int, [c_void_p, POINTER(AddNorm)] + _WORK),
+    "semidetr_add_norm_forward_mixed": (c_int, [c_void_p, POINTER(AddNormMixed)] + _WORK),
+    "semidetr_add_norm_backward_mixed": (c_int, [c_void_p, POINTER(AddNormMixed)] + _WORK),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so
@@ -307,6 +320,29 @@ def rows_f32(t):
     if t.dtype != torch.float32:
         t = t.float()
     if t.stride(2) != 1 or t.data_ptr() % 16 or t.stride(0) % 4 or t.stride(1) % 4:
+        t = t.contiguous()
+    return t
+
+
+def row_type(dtype):
+    """The ``SEMIDETR_ROW_*`` code of a torch dtype (``ROW_TYPES``); anything but fp32, fp16 and bf16 is a ``TypeError``."""
+    code = _ROW_TYPE_OF.get(dtype)
+    if code is None:
+        raise TypeError(f"rows of {dtype} are not built (float32, float16, bfloat16)")
+    return code
+
+
+_ROW_TYPE_OF = {torch.float32: ROW_TYPES["SEMIDETR_ROW_F32"], torch.float16: ROW_TYPES["SEMIDETR_ROW_FP16"],
+                torch.bfloat16: ROW_TYPES["SEMIDETR_ROW_BF16"]}
+
+
+def rows_native(t):
+    """``rows_f32`` that keeps the dtype (fp32, fp16 or bf16): a 3-D tensor as the mixed kernels read it, detached, last stride
+    1, both leading strides non-negative multiples of 4 elements, base 16-byte (fp32) or 8-byte (16-bit) aligned; copied only
+    where it is not.  A 16-bit slice whose rows start 8 bytes into a 16-byte line stays in place."""
+    t = t.detach()
+    row_type(t.dtype)
+    if t.stride(2) != 1 or t.data_ptr() % (16 if t.dtype == torch.float32 else 8) or t.stride(0) % 4 or t.stride(1) % 4:
         t = t.contiguous()
     return t
 

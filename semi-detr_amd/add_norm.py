@@ -6,9 +6,10 @@ transformer, ``x = x + dropout(branch); x = norm(x)`` (detr_od/models/utils/tran
 ``layer_norm(x + residual) + pos``: one launch forward, two backward (one where neither ``weight`` nor ``bias`` needs a
 gradient), on the current stream, with no host synchronisation and no ``.item()``.  The sum ``x + residual`` never reaches
 memory: the op saves ``x``, ``residual``, ``weight`` and the per-row ``mean`` and ``rstd``.  ``x``, ``residual``, ``pos`` and the
-upstream gradients are read through the strides of their two leading dimensions (last stride 1, rows 16-byte aligned, copied
-only where they are not), so the decoder's ``(nq, bs, 256)`` views and transposes are read in place.  The gradient of
-``residual`` is the tensor returned for ``x``, and the gradient of ``pos`` is the upstream gradient of the second output itself.
+upstream gradients are read through the strides of their two leading dimensions (last stride 1, fp32 rows 16-byte and 16-bit
+rows 8-byte aligned, copied only where they are not: ``_lib.rows_native``), so the decoder's ``(nq, bs, 256)`` views and
+transposes are read in place.  The gradient of ``residual`` is the tensor returned for ``x`` where their dtypes agree, and the
+gradient of ``pos`` is the upstream gradient of the second output itself where theirs do.
 
 ``LayerNorm`` is the drop-in for ``nn.LayerNorm(256)`` (``weight`` / ``bias`` under the same names, so a reference
 ``state_dict`` loads with ``strict=True``); ``convert_layer_norms(module)`` replaces the qualifying children of a built model in
@@ -16,15 +17,19 @@ place, adopting their ``Parameter`` objects.  ``encoder_layer_forward``, ``encod
 re-state the reference's layer control flow with the fused epilogue; ``registry.bind_layer_epilogues()`` binds them.
 
 Dtypes.  ``x``, ``residual``, ``pos``, ``weight`` and ``bias`` may each be fp32, fp16 or bf16, in any mixture; every one is
-up-cast exactly, the arithmetic is fp32, and each result is rounded once on its way out (``q`` from the unrounded ``y``).  What
+up-cast exactly, the arithmetic is fp32, and each result is rounded once on its way out (``q`` from the unrounded ``y``).  The
+rows are read and written in their own dtypes INSIDE the kernels (``semidetr_add_norm_*_mixed``; an all-fp32 call keeps the
+``*_f32`` entry points): every result is allocated in its final dtype, the 16-bit tensors that were saved are what the backward
+reads, and where ``x`` and ``residual`` differ in dtype the one ``dx`` of the backward launch leaves in both.  No cast pass
+touches a ``(rows, 256)`` tensor; only the 256-element parameter vectors and their gradients are converted by torch.  What
 comes back has the dtype stock torch gives ``F.layer_norm(x + residual, ...)`` and ``... + pos`` in the caller's autocast state:
 under enabled CUDA autocast ``y`` and ``q`` are fp32 whatever came in (``layer_norm`` is on autocast's fp32 list), so the fp32
 residual stream of a layer stays fp32 although the branch added to it is 16-bit; outside autocast ``y`` has the promoted type of
 ``x`` and ``residual`` and ``q`` that of ``y`` and ``pos`` (a ``.half()`` module: all fp16; the parameters' dtype plays no part).
 Every gradient has the dtype of the tensor it belongs to.
 
-Not built: widths other than 256, 16-bit I/O inside the kernel (16-bit inputs are computed in fp32),
-``normalize_before``, fusing ``norm3`` with the decoder's final ``norm``, the bias of ``linear2`` / ``out_proj``.
+Not built: widths other than 256, rows of other dtypes than fp32 / fp16 / bf16, ``normalize_before``,
+fusing ``norm3`` with the decoder's final ``norm``, the bias of ``linear2`` / ``out_proj``.
 """
 import ctypes
 
@@ -36,17 +41,20 @@ from . import _lib
 
 DIM = 256
 _Params = _lib.AddNorm
+_F32 = torch.float32
+_ROW_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
 
 
 def _rows3(t):
-    """A ``(..., 256)`` tensor as ``(rows0, rows1, 256)`` for the kernel (``_lib.rows_f32``); ``None`` stays ``None``."""
+    """A ``(..., 256)`` tensor as ``(rows0, rows1, 256)`` for the kernels, in its own dtype (``_lib.rows_native``); ``None``
+    stays ``None``."""
     if t is None:
         return None
     if t.dim() == 2:
         t = t.unsqueeze(0)
     elif t.dim() != 3:
         t = t.reshape(1, -1, t.shape[-1])
-    return _lib.rows_f32(t)
+    return _lib.rows_native(t)
 
 
 def _vector(t):
@@ -67,6 +75,9 @@ def _check(x, residual, weight, bias, pos):
     for t, what in ((x, "x"), (residual, "residual"), (weight, "weight"), (bias, "bias"), (pos, "pos")):
         if t is not None and not t.is_cuda:
             raise RuntimeError(f"add_layer_norm: {what} must live on the GPU (no CPU fallback)")
+    for t, what in ((x, "x"), (residual, "residual"), (pos, "pos")):
+        if t is not None and t.dtype not in _ROW_DTYPES:
+            raise NotImplementedError(f"add_layer_norm: {what} is {t.dtype}; rows of float32, float16 and bfloat16 are built")
     if x.numel() // DIM >= 2 ** 31:
         raise ValueError("add_layer_norm: too many rows (rows < 2^31)")
 
@@ -85,56 +96,88 @@ def _result_dtypes(x, residual, pos):
     return y, y if pos is None else torch.promote_types(y, pos)
 
 
-def add_layer_norm_forward(x, residual, weight, bias, eps=1e-5, pos=None):
-    """The forward launch alone, without autograd: ``(y, q, mean, rstd)`` in fp32; ``y`` and ``q`` contiguous in the shape of
-    ``x`` (``q`` is ``None`` without ``pos``), ``mean`` and ``rstd`` of ``rows`` elements."""
+def _all_f32(*tensors_and_dtypes):
+    """whether every tensor / dtype given (``None``: absent) is fp32: the call goes to the ``*_f32`` entry points"""
+    return all(t is None or (t if isinstance(t, torch.dtype) else t.dtype) == _F32 for t in tensors_and_dtypes)
+
+
+def _block(xr, eps, operands, mixed):
+    """The parameter block of a launch -- ``semidetr_add_norm``, or ``semidetr_add_norm_mixed`` with the type code of every
+    operand -- with sizes, ``eps`` and the row operands ``{name: (rows0, rows1, 256) tensor or None}`` set."""
+    p = _lib.AddNormMixed() if mixed else _Params()
+    p.rows0, p.rows1, p.dim, p.eps = xr.shape[0], xr.shape[1], DIM, eps
+    for name, t in operands.items():
+        _lib.set_rows(p, name, t)
+        if mixed and t is not None:
+            setattr(p, name + "_type", _lib.row_type(t.dtype))
+    return p
+
+
+def _set_results(p, results, mixed):
+    """``results``: {name: contiguous result tensor or None}, each with its type code where the block is the mixed one"""
+    for name, t in results.items():
+        if t is not None:
+            setattr(p, name, t.data_ptr())
+            if mixed:
+                setattr(p, name + "_type", _lib.row_type(t.dtype))
+
+
+def add_layer_norm_forward(x, residual, weight, bias, eps=1e-5, pos=None, dtypes=(_F32, _F32)):
+    """The forward launch alone, without autograd: ``(y, q, mean, rstd)``; ``y`` and ``q`` contiguous in the shape of ``x``
+    (``q`` is ``None`` without ``pos``) and in fp32 unless ``dtypes = (dtype of y, dtype of q)`` asks for fp16 or bf16 (rounded
+    once by the kernel); ``mean`` and ``rstd`` fp32 of ``rows`` elements."""
     _check(x, residual, weight, bias, pos)
-    return _forward(x, residual, weight, bias, eps, pos)
+    return _forward(x, residual, weight, bias, eps, pos, dtypes)
 
 
-def _forward(x, residual, weight, bias, eps, pos):
+def _forward(x, residual, weight, bias, eps, pos, dtypes):
     dev = x.device
     rows = x.numel() // DIM
-    y = torch.empty(x.shape, dtype=torch.float32, device=dev)
-    q = torch.empty(x.shape, dtype=torch.float32, device=dev) if pos is not None else None
+    y = torch.empty(x.shape, dtype=dtypes[0], device=dev)
+    q = torch.empty(x.shape, dtype=dtypes[1], device=dev) if pos is not None else None
     mean = torch.empty((rows,), dtype=torch.float32, device=dev)
     rstd = torch.empty((rows,), dtype=torch.float32, device=dev)
     if rows == 0:
         return y, q, mean, rstd
     xr, rr, pr, w, b = _rows3(x), _rows3(residual), _rows3(pos), _vector(weight), _vector(bias)
-    p = _Params()
-    p.rows0, p.rows1, p.dim, p.eps = xr.shape[0], xr.shape[1], DIM, eps
-    for name, t in (("x", xr), ("residual", rr), ("pos", pr)):
-        _lib.set_rows(p, name, t)
-    p.weight, p.bias, p.y, p.mean, p.rstd = w.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-    if q is not None:
-        p.q = q.data_ptr()
-    _lib.call("semidetr_add_norm_forward_f32", dev, ctypes.byref(p), None, 0)
+    mixed = not _all_f32(xr, rr, pr, y, q)
+    p = _block(xr, eps, dict(x=xr, residual=rr, pos=pr), mixed)
+    p.weight, p.bias, p.mean, p.rstd = w.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr()
+    _set_results(p, dict(y=y, q=q), mixed)
+    _lib.call("semidetr_add_norm_forward_mixed" if mixed else "semidetr_add_norm_forward_f32", dev, ctypes.byref(p), None, 0)
     return y, q, mean, rstd
 
 
-def add_layer_norm_backward(gy, gq, x, residual, weight, mean, rstd, need_weight=True, need_bias=True):
-    """The backward launches alone: ``(dx, dweight, dbias)`` in fp32 from the upstream gradients of ``y`` and ``q`` (either may
-    be ``None``) and what the forward saved; ``dweight`` / ``dbias`` are ``None`` where not needed."""
+def add_layer_norm_backward(gy, gq, x, residual, weight, mean, rstd, need_weight=True, need_bias=True, dtype=_F32):
+    """The backward launches alone: ``(dx, dweight, dbias)`` from the upstream gradients of ``y`` and ``q`` (either may be
+    ``None``) and what the forward saved; ``dx`` in fp32 unless ``dtype`` asks for fp16 or bf16 (rounded once by the kernel),
+    ``dweight`` / ``dbias`` fp32, ``None`` where not needed."""
+    dx, _, _, dw, db = _backward(gy, gq, x, residual, weight, mean, rstd, need_weight, need_bias, dtype, None, None)
+    return dx, dw, db
+
+
+def _backward(gy, gq, x, residual, weight, mean, rstd, need_weight, need_bias, x_dtype, residual_dtype, pos_dtype):
+    """One call of the backward entry point: ``(grad_x, grad_residual, grad_pos, dweight, dbias)``.  The one fp32 ``dx`` leaves
+    as ``grad_x`` in ``x_dtype`` and / or as ``grad_residual`` in ``residual_dtype``, ``gq`` as ``grad_pos`` in ``pos_dtype``;
+    ``None``: not wanted (``x_dtype`` and ``residual_dtype`` not both)."""
     dev = x.device
     xr, rr, gyr, gqr, w = _rows3(x), _rows3(residual), _rows3(gy), _rows3(gq), _vector(weight)
     rows = xr.shape[0] * xr.shape[1]
-    dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
+    gx, gres, gpos = (None if d is None else torch.empty(x.shape, dtype=d, device=dev) for d in (x_dtype, residual_dtype, pos_dtype))
     dw = torch.empty((DIM,), dtype=torch.float32, device=dev) if need_weight else None
     db = torch.empty((DIM,), dtype=torch.float32, device=dev) if need_bias else None
-    p = _Params()
-    p.rows0, p.rows1, p.dim, p.eps = xr.shape[0], xr.shape[1], DIM, 0.0
-    for name, t in (("x", xr), ("residual", rr), ("gy", gyr), ("gq", gqr)):
-        _lib.set_rows(p, name, t)
-    p.weight, p.mean, p.rstd, p.grad_x = w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr()
+    mixed = not (_all_f32(xr, rr, gyr, gqr, gx) and gres is None and gpos is None)
+    p = _block(xr, 0.0, dict(x=xr, residual=rr, gy=gyr, gq=gqr), mixed)
+    p.weight, p.mean, p.rstd = w.data_ptr(), mean.data_ptr(), rstd.data_ptr()
+    _set_results(p, dict(grad_x=gx, grad_residual=gres, grad_pos=gpos) if mixed else dict(grad_x=gx), mixed)
     work, nbytes = None, 0
     if need_weight or need_bias:
         p.grad_weight = dw.data_ptr() if need_weight else None
         p.grad_bias = db.data_ptr() if need_bias else None
         nbytes = _lib.lib().semidetr_add_norm_workspace_bytes(rows)
         work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    _lib.call("semidetr_add_norm_backward_f32", dev, ctypes.byref(p), work, nbytes)
-    return dx, dw, db
+    _lib.call("semidetr_add_norm_backward_mixed" if mixed else "semidetr_add_norm_backward_f32", dev, ctypes.byref(p), work, nbytes)
+    return gx, gres, gpos, dw, db
 
 
 class AddLayerNormFunction(torch.autograd.Function):
@@ -142,14 +185,14 @@ class AddLayerNormFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, residual, weight, bias, eps, pos):
-        y, q, mean, rstd = _forward(x, residual, weight, bias, eps, pos)          # add_layer_norm has checked the arguments
+        dtypes = (x.dtype, None if residual is None else residual.dtype, weight.dtype, bias.dtype,
+                  None if pos is None else pos.dtype)
+        # add_layer_norm has checked the arguments; every result is allocated in, and written by the kernel in, its final dtype
+        y, q, mean, rstd = _forward(x, residual, weight, bias, eps, pos, _result_dtypes(*dtypes[:2], dtypes[4]))
         ctx.save_for_backward(x, residual, weight, mean, rstd)
         ctx.set_materialize_grads(False)
-        ctx.dtypes = (x.dtype, None if residual is None else residual.dtype, weight.dtype, bias.dtype,
-                      None if pos is None else pos.dtype)
-        y_dtype, q_dtype = _result_dtypes(*ctx.dtypes[:2], ctx.dtypes[4])
-        y16 = _lib.cast(y, y_dtype)
-        return y16 if pos is None else (y16, _lib.cast(q, q_dtype))
+        ctx.dtypes = dtypes
+        return y if pos is None else (y, q)
 
     @staticmethod
     @once_differentiable
@@ -158,20 +201,29 @@ class AddLayerNormFunction(torch.autograd.Function):
         need, dt = ctx.needs_input_grad, ctx.dtypes
         if gy is None and gq is None:
             return (None,) * 6
-        gpos = _lib.cast(gq, dt[4]) if need[5] and gq is not None else None
+        want_pos = need[5] and gq is not None
+        if not any(need[:4]) or x.numel() == 0:
+            gpos = _lib.cast(gq, dt[4]) if want_pos else None            # no launch for the gradient of pos alone
         if not any(need[:4]):
             return None, None, None, None, None, gpos
+        want_res = residual is not None and need[1]
         if x.numel() == 0:                   # no rows, no launch: empty dx, zero sums
-            dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            gx = torch.empty(x.shape, dtype=dt[0], device=x.device) if need[0] else None
+            gres = (gx if gx is not None and dt[1] == dt[0] else torch.empty(x.shape, dtype=dt[1], device=x.device)) if want_res else None
             dw = torch.zeros((DIM,), dtype=torch.float32, device=x.device) if need[2] else None
             db = torch.zeros((DIM,), dtype=torch.float32, device=x.device) if need[3] else None
-        else:
-            dx, dw, db = add_layer_norm_backward(gy, gq, x, residual, weight, mean, rstd, need[2], need[3])
-        gx = _lib.cast(dx, dt[0]) if need[0] else None
-        gres = None
-        if residual is not None and need[1]:
-            gres = gx if gx is not None and dt[1] == dt[0] else _lib.cast(dx, dt[1])
-        return gx, gres, _lib.cast(dw, dt[2]), _lib.cast(db, dt[3]), None, gpos
+            return gx, gres, _lib.cast(dw, dt[2]), _lib.cast(db, dt[3]), None, gpos
+        # dx leaves once per dtype asked for: the gradient of residual is the tensor of x's where the dtypes agree, and the
+        # gradient of pos is gq itself where theirs do; a call for the parameters' gradients alone still writes x's
+        both = need[0] and want_res and dt[1] != dt[0]
+        gx, gres, gpos, dw, db = _backward(gy, gq, x, residual, weight, mean, rstd, need[2], need[3],
+                                           dt[0] if need[0] or not want_res else dt[1], dt[1] if both else None,
+                                           dt[4] if want_pos and gq.dtype != dt[4] else None)
+        if want_pos and gpos is None:
+            gpos = gq
+        if want_res and not both:
+            gres = gx
+        return gx if need[0] else None, gres, _lib.cast(dw, dt[2]), _lib.cast(db, dt[3]), None, gpos
 
 
 def add_layer_norm(x, residual, weight, bias, eps=1e-5, pos=None):

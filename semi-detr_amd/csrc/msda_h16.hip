@@ -36,44 +36,7 @@ constexpr int kD = 32;              // channels per head of the fast path
 constexpr int kMaxLevels = 32;
 thread_local const char *g_last_kernels = "";
 
-// ---- the two storage types: exact up-cast, one round-to-nearest-even down-cast ----------------------------------------
-template <typename T16>
-struct Cvt;
-template <>
-struct Cvt<__half> {
-    static __device__ __forceinline__ float up(unsigned bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
-    static __device__ __forceinline__ unsigned down(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
-};
-template <>
-struct Cvt<__hip_bfloat16> {
-    static __device__ __forceinline__ float up(unsigned bits) { return __uint_as_float(bits << 16); }
-    static __device__ __forceinline__ unsigned down(float f)
-    {
-        return __builtin_bit_cast(unsigned short, __float2bfloat16(f));      // v_cvt_pk_bf16_f32 on gfx950
-    }
-};
-// four channels of a row = two dwords (channel 0 in the low half of the first)
-template <typename T16>
-__device__ __forceinline__ float4 unpack4(float2 raw)
-{
-    const unsigned a = __float_as_uint(raw.x), b = __float_as_uint(raw.y);
-    return make_float4(Cvt<T16>::up(a & 0xffffu), Cvt<T16>::up(a >> 16), Cvt<T16>::up(b & 0xffffu), Cvt<T16>::up(b >> 16));
-}
-template <typename T16>
-__device__ __forceinline__ unsigned pack2(float lo, float hi)
-{
-    return Cvt<T16>::down(lo) | (Cvt<T16>::down(hi) << 16);
-}
-template <typename T16>
-__device__ __forceinline__ float ld16(const T16 *p)
-{
-    return Cvt<T16>::up(*reinterpret_cast<const unsigned short *>(p));
-}
-template <typename T16>
-__device__ __forceinline__ void st16(T16 *p, float f)
-{
-    *reinterpret_cast<unsigned short *>(p) = (unsigned short)Cvt<T16>::down(f);
-}
+#include "cvt16.h"                   // the two storage types: Cvt<T16>, unpack4, pack2, ld16, st16
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
