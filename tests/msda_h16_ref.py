@@ -69,10 +69,12 @@ class Bounded16:
         return np.where(np.isfinite(got), r, np.inf)
 
 
-def reference(value16, shapes, loc, attn, gout16, dtype):
+def reference(value16, shapes, loc, attn, gout16, dtype, exact=None):
     """value16 / gout16: float32 arrays holding 16-bit values exactly (round16).  -> dict of 'out', 'grad_value' (Bounded16) and
-    'grad_loc', 'grad_attn' (msda_ref64.Bounded, fp32 bound); without gout16 only 'out'."""
-    r = R.msda(np.asarray(value16, np.float64), shapes, loc, attn, None if gout16 is None else np.asarray(gout16, np.float64))
+    'grad_loc', 'grad_attn' (msda_ref64.Bounded, fp32 bound); without gout16 only 'out'.  exact: msda_ref64.msda's flag of the
+    samples whose fp32 pixel coordinates carry no rounding (locations stay fp32 in this op, so it means the same here)."""
+    r = R.msda(np.asarray(value16, np.float64), shapes, loc, attn, None if gout16 is None else np.asarray(gout16, np.float64),
+               exact=exact)
     return {k: (Bounded16(v, dtype) if k in ROUNDED else v) for k, v in r.items()}
 
 

@@ -47,6 +47,20 @@ element e formed as a sum of products, any summation order and any grouping give
   * fp64 kernels: u = 2^-53, tiny with 2^-1022, and twice the bound.
 
 The factor 2, DEPTH and the prologue constants are fixed here from this derivation; no test scales the bound.
+
+Exact samples (msda(..., exact=...), tests/msda_lattice_cases.py).  delta pays for the rounding of x = fl(fl(lx * W) - 0.5).  Where
+lx * W and lx * W - 0.5 are both fp32 numbers -- a dyadic lx on a level whose extent makes the product dyadic too: pixel centres,
+the skip edges x = -1 and x = W, normalised 0 and 1 -- neither operation rounds, fused into one FMA or not, so every correct kernel
+holds the very x of this reference and no delta is owed: C_e gets nothing from the sample, it is never in the kink set and never an
+edge sample.  What the contract says AT such a point is then determinate and is judged like anything else: the cell is floor(x), so
+on a pixel-centre line the far corner has weight exactly 0 and grad_loc is the right-hand derivative; the skip test is strict, so
+x = -1 and x = W contribute nothing and have zero gradients; a corner off the map (or padded) is zero padding even at weight 0.
+The flag is the caller's claim; tests/test_msda_lattice_ref.py proves it bit for bit for every flagged sample.  For the fused
+prologue the location is formed in the kernel (ref + off * rcp(W)), so only a sample whose offset is exactly 0 may be flagged.
+
+Non-finite samples.  A sample whose pixel coordinate is NaN, infinite or beyond fp32's range fails every comparison of the skip
+test: it is skipped, contributes nothing and has zero gradients, like any other skipped sample, and it has zero sensitivity (no
+rounding moves it onto the map).
 """
 import numpy as np
 
@@ -154,11 +168,22 @@ def _geometry(loc_c, H, W, start, M, clamp=None):
     return pix * M + m, ok, np.where(ok, c, 0.0), np.where(ok, dcx, 0.0), np.where(ok, dcy, 0.0), x, y
 
 
-def msda(value, shapes, loc, attn, gout=None, delta=None, eps=None, mask=None, weights_hook=None):
+F32_MAX = float(np.finfo(np.float32).max)
+
+
+def non_finite(loc, shapes):
+    """Samples whose pixel coordinate is NaN, infinite or beyond fp32's range (module docstring), shape loc.shape[:-1]."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        x, y = pixel_coords(loc, shapes)
+        return ~((np.abs(x) <= F32_MAX) & (np.abs(y) <= F32_MAX))
+
+
+def msda(value, shapes, loc, attn, gout=None, delta=None, eps=None, mask=None, weights_hook=None, exact=None):
     """The op in fp64 with bounds.  value (N,S,M,D), loc (N,Lq,M,L,P,2), attn (N,Lq,M,L,P), gout (N,Lq,M*D) or None.
     delta / eps (per sample, units of u): default the reference contract's (contract_delta, 0).  mask (N,S) bool: value is
     masked_fill'ed with 0 there (NaN in padded rows never reaches a result) and grad_value is 0 there (masked_fill's backward).
-    weights_hook(a, c) -> (a, c): test mutants only (tests/test_msda_ref64.py).
+    weights_hook(a, c) -> (a, c): test mutants only (tests/test_msda_ref64.py).  exact (N,Lq,M,L,P) bool: samples whose pixel
+    coordinates the kernel holds without rounding (module docstring): delta 0, never in the kink set, never an edge sample.
     -> dict with Bounded 'out' and, with gout, 'grad_value', 'grad_loc', 'grad_attn'."""
     shapes, starts = _level_table(shapes)
     H, W = shapes[:, 0], shapes[:, 1]
@@ -167,10 +192,19 @@ def msda(value, shapes, loc, attn, gout=None, delta=None, eps=None, mask=None, w
     loc = np.asarray(loc)
     _, Lq, _, L, P, _ = loc.shape
     attn = np.asarray(attn)
+    bad = non_finite(loc, shapes)
+    if bad.any():      # skipped, zero sensitivity: moved to a finite place far off the map, so that nothing below meets inf - inf
+        loc = np.where(bad[..., None], -2.0, loc)
+        delta = None if delta is None else np.where(bad, 0.0, np.broadcast_to(delta, attn.shape))
     if delta is None:
         delta = contract_delta(loc, shapes)
+        if bad.any():
+            delta = np.where(bad, 0.0, delta)
     eps = np.zeros(attn.shape) if eps is None else np.broadcast_to(eps, attn.shape)
     delta = np.broadcast_to(delta, attn.shape)
+    if exact is not None:
+        exact = np.broadcast_to(np.asarray(exact, bool), attn.shape)
+        delta = np.where(exact, 0.0, delta)
     out = [np.zeros((N, Lq, M, D)) for _ in range(3)]
     if gout is not None:
         gout = np.asarray(gout, np.float64).reshape(N, Lq, M, D)
@@ -194,6 +228,8 @@ def msda(value, shapes, loc, attn, gout=None, delta=None, eps=None, mask=None, w
             wide = 2 * delta[n, sl] * U32
             Hf, Wf = H.astype(np.float64)[:, None], W.astype(np.float64)[:, None]
             edge = ~ok.any(-1) & (x > -1 - wide) & (y > -1 - wide) & (x < Wf + wide) & (y < Hf + wide)
+            if exact is not None:      # (already so: wide == 0 there and the skip test is strict)
+                edge &= ~exact[n, sl]
             edge_rows = None
             if edge.any():
                 tight = np.minimum(wide, 0.25)
@@ -229,6 +265,8 @@ def msda(value, shapes, loc, attn, gout=None, delta=None, eps=None, mask=None, w
                 gl[1][n, sl, ..., j] = A
                 gl[2][n, sl, ..., j] = e * np.abs(a) * (ag * sabs).sum(-1) * dl + ep * A
             kink[n, sl] = (np.abs(y - np.round(y)) <= wide) | (np.abs(x - np.round(x)) <= wide)
+            if exact is not None:      # on a line the contract is determinate: floor's cell, the right-hand derivative
+                kink[n, sl] &= ~exact[n, sl]
             # grad_value: contribution i = (query, head, sample, corner) -> row; weights a c_k times the (query, head) row of gout
             w = (a[..., None] * c).reshape(-1)
             wA = (np.abs(a)[..., None] * c).reshape(-1)
@@ -273,13 +311,17 @@ def backward(value, shapes, loc, attn, gout, **kw):
     return r["grad_value"], r["grad_loc"], r["grad_attn"]
 
 
-def fused(value, shapes, ref, off, logits, gout=None, mask=None):
+def fused(value, shapes, ref, off, logits, gout=None, mask=None, exact=None):
     """The fused prologue + op + epilogue in fp64: dict with 'out' and, with gout, 'grad_value', 'grad_offsets', 'grad_logits'
-    (and the intermediate 'grad_loc' / 'grad_attn' against the prologue's locations)."""
+    (and the intermediate 'grad_loc' / 'grad_attn' against the prologue's locations).  exact: as msda(), and only where the
+    sample's offset is exactly 0 (the kernel forms ref + off * rcp(W): with off = 0 that is ref, whatever rcp gives)."""
     shapes, _ = _level_table(shapes)
     P = np.asarray(off).shape[4]
-    pro = prologue(ref, off, logits, shapes, P)
-    res = msda(value, shapes, pro["loc"], pro["attn"], gout, delta=pro["delta"], eps=pro["eps"], mask=mask)
+    if exact is not None:
+        assert not (np.asarray(exact, bool) & (np.asarray(off) != 0).any(-1)).any(), "fused: exact needs a zero offset"
+    with np.errstate(invalid="ignore", over="ignore"):      # (non-finite offsets: msda() skips those samples)
+        pro = prologue(ref, off, logits, shapes, P)
+    res = msda(value, shapes, pro["loc"], pro["attn"], gout, delta=pro["delta"], eps=pro["eps"], mask=mask, exact=exact)
     res["prologue"] = pro
     if gout is None:
         return res

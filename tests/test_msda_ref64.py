@@ -177,3 +177,17 @@ def test_route_table_lists_every_product_route():
     assert routes == set(ROUTES), ("routes without a bounded GPU case:", routes - set(ROUTES), "stale:", set(ROUTES) - routes)
     for route, cases in ROUTES.items():
         assert cases, route
+
+
+def test_every_product_route_has_a_lattice_case():
+    """... and every one of them, with the 16-bit op's, also runs on exact lattice / skip-edge samples (tests/msda_lattice_cases.py,
+    judged with msda_ref64's `exact` flag by tests/test_gpu_msda_lattice.py)."""
+    import msda_h16_cases as C16
+    import msda_lattice_cases as LC
+    import test_gpu_msda_bounds as B
+    routes = product_routes() | {C16.FWD1, C16.FWD2, C16.FWD4, C16.FWD_GENERIC, C16.BWD, C16.BWD_GENERIC}
+    assert routes == set(LC.ROUTES), ("routes without a lattice case:", routes - set(LC.ROUTES), "stale:", set(LC.ROUTES) - routes)
+    kinds = {s["kind"] for s in LC.ALL_CASES.values()}
+    assert kinds == {"lattice", "nonfinite"}
+    for route in (B.FWD_STRIP4, B.FWD_PATCH, B.FWD_WINDOW, B.FWD_GENERIC, C16.FWD4):      # the routes the non-finite kind must reach
+        assert any(s["kind"] == "nonfinite" and s["fwd"] == route for s in LC.ALL_CASES.values()), route

@@ -27,7 +27,12 @@ def main():
                     "variant does not apply to are skipped")
     ap.add_argument("--policy", default="adaptive", choices=["adaptive", "patch", "window"],
                     help="encoder forward kernel (semidetr_msda_set_forward_policy); \"window\" sends every eligible case through msda_rw_d32")
+    ap.add_argument("--lattice", action="store_true", help="put half of the samples exactly on pixel-centre lines, skip edges and other "
+                    "positions whose fp32 pixel coordinate carries no rounding (the generator of tests/msda_lattice_cases.py)")
     a = ap.parse_args()
+    if a.lattice:      # (only then: without the option the tool needs nothing from tests/)
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import msda_lattice_cases as LC
     import semi_detr_amd  # noqa: F401  (installs the module below)
     semi_detr_amd._lib.set_forward_policy(a.policy)
     import MultiScaleDeformableAttention as MSDA
@@ -57,6 +62,9 @@ def main():
             loc = rng.random((N, Lq, M, L, P, 2)) * 1.6 - 0.3
         else:
             loc = rng.random((N, Lq, M, L, P, 2))
+        if a.lattice:
+            pos = LC._exact_positions(rng, shp, loc.shape[:-1], LC._query_pixels(shp) if enc else None, LC._valid_extents(shp, None, N), None)
+            loc = np.where(rng.random(loc.shape[:-1] + (1,)) < 0.5, pos, loc)
         value = (rng.random((N, S, M, 32)) - 0.3).astype(np.float32)
         attn = rng.random((N, Lq, M, L, P)) + 1e-5
         attn /= attn.sum((-1, -2), keepdims=True)
