@@ -9,6 +9,8 @@
 3. Layout: 16-bit slices whose rows start 8 bytes into a 16-byte line are read in place.
 4. No detour through fp32: the peak memory of ``add_layer_norm`` forward and backward.
 5. The identity contracts of the gradients of ``residual`` and ``pos``.
+6. The two instances of the one kernel template against each other: the ``*_mixed`` entry points with every type code
+   ``SEMIDETR_ROW_F32`` are bit for bit the ``*_f32`` entry points on the same buffers.
 """
 import ctypes
 
@@ -64,19 +66,20 @@ def abi_forward(x, res, pos, w, b, eps, y_dtype=F32, q_dtype=F32, mixed=True):
     return y, q, mean, rstd
 
 
-def abi_backward(gy, gq, x, res, w, mean, rstd, gx_dtype=F32, gres_dtype=None, gpos_dtype=None, mixed=True):
-    """the backward entry point itself -> grad_x, grad_residual, grad_pos, grad_weight, grad_bias (None: not asked for)"""
+def abi_backward(gy, gq, x, res, w, mean, rstd, gx_dtype=F32, gres_dtype=None, gpos_dtype=None, mixed=True, sums=True):
+    """the backward entry point itself -> grad_x, grad_residual, grad_pos, grad_weight, grad_bias (None: not asked for;
+    ``sums`` = False asks for neither parameter gradient and hands over no workspace: one launch)"""
     from semi_detr_amd import _lib
     rows = x.shape[0] * x.shape[1]
     gx, gres, gpos = (None if d is None else torch.full(x.shape, float("nan"), dtype=d, device=DEV)
                       for d in (gx_dtype, gres_dtype, gpos_dtype))
-    dw, db = (torch.full((256,), float("nan"), device=DEV) for _ in range(2))
+    dw, db = (torch.full((256,), float("nan"), device=DEV) if sums else None for _ in range(2))
     results = dict(grad_x=gx, grad_weight=dw, grad_bias=db, mean=mean, rstd=rstd, weight=w)
     if mixed:
         results.update(grad_residual=gres, grad_pos=gpos)
     p = _block(_lib.AddNormMixed if mixed else _lib.AddNorm, 0.0, dict(x=x, residual=res, gy=gy, gq=gq), results, mixed)
-    nbytes = _lib.lib().semidetr_add_norm_workspace_bytes(rows)
-    work = torch.full((nbytes // 4,), float("nan"), device=DEV)
+    nbytes = _lib.lib().semidetr_add_norm_workspace_bytes(rows) if sums else 0
+    work = torch.full((nbytes // 4,), float("nan"), device=DEV) if sums else None
     _lib.call("semidetr_add_norm_backward_mixed" if mixed else "semidetr_add_norm_backward_f32", x.device, ctypes.byref(p),
               work, nbytes)
     return gx, gres, gpos, dw, db
@@ -428,3 +431,49 @@ def test_fp16_x_with_bf16_residual_promotes_and_splits_dx(launches):
     for n, a, c in zip(("y", "dx", "dres", "dweight", "dbias"), got, plain):
         assert torch.equal(a, c.to(a.dtype)), f"{n} is not the fp32 result rounded once"
     assert torch.equal(plain[1], plain[2])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 6. the two instances of the one kernel template
+# ------------------------------------------------------------------------------------------------------------------
+# rows0 x rows1: 1 row; 5 = a partly filled batch of four; 17 crosses a backward wave's 16 rows; 67 puts a second backward
+# workgroup on a 3-row tail; 129 = three slots, an uneven chunk of the parameter sums
+INSTANCE_SHAPES = [(1, 1), (5, 1), (1, 17), (67, 1), (3, 43)]
+PRESENCE = {"residual_pos_gy_gq": dict(residual=True, pos=True, gy=True, gq=True),
+            "residual_gy": dict(residual=True, pos=False, gy=True, gq=False),
+            "pos_gq": dict(residual=False, pos=True, gy=False, gq=True)}
+INSTANCE_CASES = [(sh, pr, "contiguous") for sh in INSTANCE_SHAPES for pr in PRESENCE] + [((3, 43), "residual_pos_gy_gq", "transposed")]
+
+
+@pytest.mark.parametrize("shape,presence,layout", INSTANCE_CASES,
+                         ids=[f"r{a * b}_{a}x{b}/{pr}/{lay}" for (a, b), pr, lay in INSTANCE_CASES])
+def test_all_fp32_codes_are_the_fp32_entry_points_bit_for_bit(shape, presence, layout):
+    """Every output buffer starts as NaN, so an element one instance leaves unwritten shows; the operands are finite."""
+    have, g = PRESENCE[presence], torch.Generator().manual_seed(11 * shape[0] + shape[1])
+
+    def rows(present=True):
+        if not present:
+            return None
+        if layout == "transposed":                                   # read through a (rows1, rows0, 256) tensor's strides
+            t = torch.randn(shape[1], shape[0], 256, generator=g).to(DEV).transpose(0, 1)
+            assert not t.is_contiguous() or 1 in shape
+            return t
+        return torch.randn(*shape, 256, generator=g).to(DEV)
+    x, res, pos, gy, gq = rows(), rows(have["residual"]), rows(have["pos"]), rows(have["gy"]), rows(have["gq"])
+    w, b = (torch.randn(256, generator=g).to(DEV) for _ in range(2))
+
+    def run(mixed, sums):
+        y, q, mean, rstd = abi_forward(x, res, pos, w, b, 1e-5, mixed=mixed)
+        only_mixed = dict(gres_dtype=F32 if res is not None else None, gpos_dtype=F32 if gq is not None else None) if mixed else {}
+        gx, gres, gpos, dw, db = abi_backward(gy, gq, x, res, w, mean, rstd, mixed=mixed, sums=sums, **only_mixed)
+        return dict(y=y, q=q, mean=mean, rstd=rstd, grad_x=gx, grad_weight=dw, grad_bias=db), gres, gpos
+    for sums in (True, False):
+        (typed, gres, gpos), (plain, _, _) = run(True, sums), run(False, sums)
+        for n, t in plain.items():
+            assert (t is None) == (typed[n] is None) == (n == "q" and pos is None or n in ("grad_weight", "grad_bias") and not sums), n
+            if t is not None:
+                assert not torch.isnan(t).any() and not torch.isnan(typed[n]).any(), f"{n}: elements left unwritten"
+                assert _same_bits(typed[n], t), f"{n} (sums={sums}): the typed instance on fp32 codes is not the fp32 instance"
+        assert (gres is not None) == have["residual"] and (gpos is not None) == have["gq"]
+        assert gres is None or _same_bits(gres, typed["grad_x"]), "grad_residual is not grad_x"
+        assert gpos is None or _same_bits(gpos, gq), "grad_pos is not gq"
