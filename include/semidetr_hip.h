@@ -836,6 +836,56 @@ int semidetr_self_attn_backward_f32(void *stream, const semidetr_self_attn *para
                                     size_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same core on fp16 / bf16 operands, computed on the 16-bit MFMA (ABI 7, additive): the "operand" arithmetic beside the
+ * fp32 one above.  It is a second, named arithmetic with a numerics contract of its own, NOT the fp32 entry points on up-cast
+ * operands: the probabilities and dS are rounded to the operand type before their products.
+ *
+ * `type` is SEMIDETR_ROW_FP16 or SEMIDETR_ROW_BF16 (below) and is the element type of q, k, v, out, grad_out, grad_q, grad_k and
+ * grad_v alike; lse and the workspace are fp32.  All of them are read and written in place as 16-bit: no fp32 copy of an
+ * operand is made in memory or in LDS.  Layout as above -- q, k, v and the three gradients through their (length, batch)
+ * strides in ELEMENTS, last stride 1; out and grad_out contiguous -- but a row starts 8-byte aligned (base 8-byte aligned,
+ * strides non-negative multiples of 4), so a 16-bit slice whose rows sit 8 bytes into a 16-byte line is read in place, and
+ * grad_q and grad_k may be the two halves of one packed (len, batch, 2 * heads * 32) buffer.  mask, tile classes, the NaN row,
+ * launch counts, semidetr_self_attn_workspace_bytes and the limits are those of the fp32 pair.  No float atomics, no memset,
+ * every sum in a fixed order: bitwise reproducible.
+ *
+ * Numerics contract, in this order (u16 = 2^-11 fp16, 2^-8 bf16):
+ *   - the scores are the fp32 MFMA sum of the exact products q_id k_jd, times scale in fp32 (the fp32 score is scaled, never q:
+ *     32^-0.5 has no 16-bit representation);
+ *   - the running maximum, exp2, the row sum l and lse = m + log(l) are fp32, on the UNROUNDED probabilities;
+ *   - P is rounded once to the operand type for P V (forward) and P^T dO (dV);
+ *   - dP = dO V^T is an fp32 MFMA sum of exact products; delta_i = sum_d dO_id out_id is formed in fp32 from dO and the saved
+ *     16-bit out;
+ *   - dS = P o (dP - delta) is fp32 from the unrounded P, then rounded once to the operand type for dS K (dQ) and dS^T Q (dK);
+ *     scale is applied to the fp32 accumulators of dQ and dK;
+ *   - every result (out, grad_q, grad_k, grad_v) is rounded once, to nearest even, on the way out (fp16 overflows to inf).
+ * The order and rounding mode of the additions inside a 16-bit MFMA are not documented; the contract takes them as n exact
+ * products summed in any order with at most 2 u (u = 2^-24) relative error per addition.
+ *
+ * semidetr_self_attn_forward_h16  -- two launches (one without a mask): writes out and lse.
+ * semidetr_self_attn_backward_h16 -- three launches at most; grad_q / grad_k / grad_v may each be NULL (at least one is not).
+ * Checked on the host before any launch: type SEMIDETR_ROW_F32 or unknown, head_dim != 32, a misaligned row, a NULL operand
+ * and all three gradients NULL are SEMIDETR_E_BADARG, with a message.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct semidetr_self_attn_h16 {
+    int batch, heads, head_dim, len_q, len_k;
+    float scale;
+    int type;                                             /* SEMIDETR_ROW_FP16 or SEMIDETR_ROW_BF16: every 16-bit tensor */
+    const void *q, *k, *v;
+    int64_t q_stride[2], k_stride[2], v_stride[2];        /* (length, batch) strides in elements */
+    const uint8_t *mask;                                  /* (len_q, len_k) or NULL */
+    void *out;                                            /* forward: written; backward: read */
+    float *lse;
+    const void *grad_out;                                 /* backward only from here on */
+    void *grad_q, *grad_k, *grad_v;
+    int64_t gq_stride[2], gk_stride[2], gv_stride[2];
+} semidetr_self_attn_h16;
+int semidetr_self_attn_forward_h16(void *stream, const semidetr_self_attn_h16 *params /* host */, void *workspace,
+                                   size_t workspace_bytes);
+int semidetr_self_attn_backward_h16(void *stream, const semidetr_self_attn_h16 *params /* host */, void *workspace,
+                                    size_t workspace_bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * Residual add + LayerNorm + positional add (ABI 7, additive): the epilogue of a transformer sub-block and the with_pos_embed
  * that opens the next one, row width 256.
  *

@@ -29,7 +29,7 @@ from .dn_query import consistency_queries, prepare_for_cdn, prepare_for_cdn_plus
 from .query_select import gen_encoder_output_proposals, select_queries, two_stage_queries  # noqa: E402,F401
 from .detect import PendingDetections, detection_results, get_bboxes  # noqa: E402,F401
 from .consis_loss import ConsistencyLossFunction, consistency_loss  # noqa: E402,F401
-from .self_attn import (MaskedAttentionFunction, MultiheadAttention, convert_self_attention,  # noqa: E402,F401
+from .self_attn import (MaskedAttentionFunction, MaskedAttentionH16Function, MultiheadAttention, convert_self_attention,  # noqa: E402,F401
                         masked_attention)
 from .add_norm import (AddLayerNormFunction, LayerNorm, add_layer_norm, convert_layer_norms, decoder_layer_forward,  # noqa: E402,F401
                        decoder_layer_forward_ca, decoder_layer_forward_ffn, decoder_layer_forward_sa, encoder_forward,
@@ -45,6 +45,6 @@ __all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttnMix
            "FocalLoss", "SetLossSegment", "loss_set", "set_losses", "prepare_for_cdn", "prepare_for_cdn_plus",
            "prepare_unsup_cdn", "consistency_queries", "gen_encoder_output_proposals", "select_queries", "two_stage_queries",
            "get_bboxes", "detection_results", "PendingDetections", "consistency_loss", "ConsistencyLossFunction",
-           "masked_attention", "MaskedAttentionFunction", "MultiheadAttention", "convert_self_attention",
+           "masked_attention", "MaskedAttentionFunction", "MaskedAttentionH16Function", "MultiheadAttention", "convert_self_attention",
            "add_layer_norm", "AddLayerNormFunction", "LayerNorm", "convert_layer_norms", "encoder_layer_forward", "encoder_forward",
            "decoder_layer_forward", "decoder_layer_forward_sa", "decoder_layer_forward_ca", "decoder_layer_forward_ffn"]

@@ -95,6 +95,12 @@ class SelfAttn(ctypes.Structure):
                 + _f(_STRIDE2, "gq_stride gk_stride gv_stride"))
 
 
+class SelfAttnH16(ctypes.Structure):
+    _fields_ = (_f(c_int, "batch heads head_dim len_q len_k") + _f(c_float, "scale") + _f(c_int, "type") + _f(c_void_p, "q k v")
+                + _f(_STRIDE2, "q_stride k_stride v_stride") + _f(c_void_p, "mask out lse grad_out grad_q grad_k grad_v")
+                + _f(_STRIDE2, "gq_stride gk_stride gv_stride"))
+
+
 class AddNorm(ctypes.Structure):
     _fields_ = (_f(c_int, "rows0 rows1 dim") + _f(c_float, "eps") + _f(c_void_p, "x residual pos gy gq")
                 + _f(_STRIDE2, "x_stride residual_stride pos_stride gy_stride gq_stride")
@@ -112,7 +118,8 @@ class AddNormMixed(ctypes.Structure):
 # C struct -> mirror, in the header's order
 STRUCTS = {"semidetr_cost_params": CostParams, "semidetr_set_loss_segment": SetLossSegment, "semidetr_dn_layout": DnLayout,
            "semidetr_dn_build": DnBuild, "semidetr_dn_consistency": DnConsistency, "semidetr_consis_layer": ConsisLayer,
-           "semidetr_consis_loss": ConsisLoss, "semidetr_self_attn": SelfAttn, "semidetr_add_norm": AddNorm,
+           "semidetr_consis_loss": ConsisLoss, "semidetr_self_attn": SelfAttn, "semidetr_self_attn_h16": SelfAttnH16,
+           "semidetr_add_norm": AddNorm,
            "semidetr_add_norm_mixed": AddNormMixed}
 _SEGS, _WORK = POINTER(SetLossSegment), [c_void_p, c_size_t]        # a segment table; the (workspace, workspace_bytes) pair
 
@@ -194,6 +201,8 @@ SIGNATURES = {
     "semidetr_self_attn_workspace_bytes": (c_size_t, [c_int] * 4),
     "semidetr_self_attn_forward_f32": (c_int, [c_void_p, POINTER(SelfAttn)] + _WORK),
     "semidetr_self_attn_backward_f32": (c_int, [c_void_p, POINTER(SelfAttn)] + _WORK),
+    "semidetr_self_attn_forward_h16": (c_int, [c_void_p, POINTER(SelfAttnH16)] + _WORK),
+    "semidetr_self_attn_backward_h16": (c_int, [c_void_p, POINTER(SelfAttnH16)] + _WORK),
     # residual add + LayerNorm + positional add (add_norm.py)
     "semidetr_add_norm_workspace_bytes": (c_size_t, [c_int64]),
     "semidetr_add_norm_forward_f32": (c_int, [c_void_p, POINTER(AddNorm)] + _WORK),

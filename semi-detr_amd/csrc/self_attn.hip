@@ -4,6 +4,7 @@
 // exact k-ordered fmaf chain), fp32 out.  The (Lq, Lk) scores never reach memory.
 //
 //   sattn_class_kernel   one wave per 32 x 32 tile of the byte mask: 0 = every in-range element blocked, 2 = none, 1 = mixed
+//                        (self_attn_tiles.h, shared with the 16-bit arithmetic of self_attn_h16.hip)
 //   sattn_q_kernel<0>    forward: workgroup = 2 waves = 64 queries of one (image, head), wave = 32 queries; key tiles of 32
 //                        through LDS
 //   sattn_q_kernel<1>    backward, same geometry: delta_i = sum_d dO_id O_id (written for the next launch), P = exp(s - lse), dQ
@@ -32,32 +33,16 @@
 
 namespace {
 
-constexpr int kD = 32;                       // head dimension
-constexpr int kTile = 32;                    // rows of an MFMA tile: queries per wave, keys per staged tile
-constexpr int kWaves = 2, kThreads = 64 * kWaves;
+#include "self_attn_tiles.h"
+
 constexpr int kPad = kD + 1;                 // LDS row stride of an image read down a column of lanes (A = X[row c][d])
-constexpr float kLog2e = 1.44269504088896340736f;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Launch {
+struct Launch : Tiles {
     semidetr_self_attn p;
-    const uint8_t *cls;        // (nqt, nkt) tile classes, NULL without a mask
     float *delta;              // (B, H, Lq)
-    int nqt, nkt;              // 32-row tiles of queries / keys
 };
 
-__device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
-__device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ int tile_class(const Launch &L, int qt, int kt)
-{
-    if (qt >= L.nqt || kt >= L.nkt) return 0;
-    return L.cls ? (int)L.cls[qt * L.nkt + kt] : 2;
-}
 
 // A tile of 32 rows x 32 floats of `base` (row stride s0 elements, rows from row0, valid below `rows`) in the registers of the
 // workgroup's 128 threads: two float4 per thread; rows past the end read as zeros.
@@ -83,24 +68,6 @@ __device__ __forceinline__ void tile_store(float *lds, const TileRegs &t, float 
         float *d = lds + row * kPad + 4 * c4;
         d[0] = t.v[i].x * mul; d[1] = t.v[i].y * mul; d[2] = t.v[i].z * mul; d[3] = t.v[i].w * mul;
     }
-}
-
-__global__ __launch_bounds__(64) void sattn_class_kernel(const uint8_t *__restrict__ mask, int Lq, int Lk, int nkt,
-                                                         uint8_t *__restrict__ cls)
-{
-    const int kt = blockIdx.x, qt = blockIdx.y, lane = threadIdx.x;
-    const int q = qt * kTile + (lane >> 1), k0 = kt * kTile + 16 * (lane & 1);
-    bool open = false, blocked = false;
-    if (q < Lq) {
-        for (int j = 0; j < 16; ++j) {
-            if (k0 + j >= Lk) break;
-            const bool b = mask[(int64_t)q * Lk + k0 + j] != 0;
-            open |= !b;
-            blocked |= b;
-        }
-    }
-    const bool any_open = __ballot(open) != 0, any_blocked = __ballot(blocked) != 0;
-    if (lane == 0) cls[qt * nkt + kt] = any_open ? (any_blocked ? 1 : 2) : 0;
 }
 
 // the 16 elements d = 2 s + h of a row, times mul
@@ -142,44 +109,6 @@ __device__ __forceinline__ void row_store(float *dst, const f32x16 &o, int h)
     for (int g = 0; g < 4; ++g)
         *reinterpret_cast<float4 *>(dst + 8 * g + 4 * h) = make_float4(o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]);
 }
-
-// The classes of 64 consecutive tiles at a time, one tile per lane, as wave-uniform bit masks: which tiles the workgroup stages
-// (a tile open for either wave) and which this wave multiplies.  BY_KEY walks the key tiles of the query tiles (a0, a0 + 1),
-// otherwise the query tiles of the key tiles (a0, a0 + 1).
-template <bool BY_KEY>
-struct TileScan {
-    uint64_t open, mine, mixed;
-    int base, n, a0, wv;
-    __device__ __forceinline__ TileScan(const Launch &L, int a0_, int wv_) : n(BY_KEY ? L.nkt : L.nqt), a0(a0_), wv(wv_) { load(L, 0); }
-    __device__ __forceinline__ void load(const Launch &L, int b)
-    {
-        base = b;
-        const int t = b + (threadIdx.x & 63);
-        const int c0 = BY_KEY ? tile_class(L, a0, t) : tile_class(L, t, a0);
-        const int c1 = BY_KEY ? tile_class(L, a0 + 1, t) : tile_class(L, t, a0 + 1);
-        const int cm = wv ? c1 : c0;
-        open = __ballot((c0 | c1) != 0);
-        mine = __ballot(cm != 0);
-        mixed = __ballot(cm == 1);
-    }
-    // the first tile >= t that the workgroup stages, n when there is none
-    __device__ __forceinline__ int next(const Launch &L, int t)
-    {
-        while (t < n) {
-            if (t >= base + 64) load(L, t & ~63);
-            const uint64_t m = open >> (t - base);
-            if (m) return t + __builtin_ctzll(m);
-            t = base + 64;
-        }
-        return n;
-    }
-    // this wave's class of tile t of the loaded 64
-    __device__ __forceinline__ int cls(int t) const
-    {
-        const int s = t - base;
-        return ((mine >> s) & 1) ? (((mixed >> s) & 1) ? 1 : 2) : 0;
-    }
-};
 
 template <bool BACKWARD>
 __global__ __launch_bounds__(kThreads) void sattn_q_kernel(const Launch L)
@@ -347,22 +276,13 @@ __global__ __launch_bounds__(kThreads) void sattn_dkv_kernel(const Launch L)
 bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15) == 0; }
 bool rows_ok(const void *ptr, const int64_t *stride) { return aligned16(ptr) && stride[0] >= 0 && stride[1] >= 0 && stride[0] % 4 == 0 && stride[1] % 4 == 0; }
 
-size_t delta_bytes(int batch, int heads, int len_q) { return (((size_t)batch * heads * len_q * sizeof(float)) + 15) & ~(size_t)15; }
-
 // Host-side check of the parameter block + launch geometry.  Returns SEMIDETR_OK or an error (message set).
 int plan(const semidetr_self_attn *params, void *workspace, size_t workspace_bytes, Launch &L, int for_backward)
 {
     SEMIDETR_REQUIRE(params, SEMIDETR_E_BADARG, "self_attn: null pointer (parameter block)");
     const semidetr_self_attn &p = params[0];
     SEMIDETR_REQUIRE(p.head_dim == kD, SEMIDETR_E_BADARG, "self_attn: head dimension %d (only %d is built)", p.head_dim, kD);
-    SEMIDETR_REQUIRE(p.batch > 0 && p.heads > 0 && p.len_q > 0 && p.len_k > 0, SEMIDETR_E_BADARG,
-                     "self_attn: bad sizes (B=%d H=%d Lq=%d Lk=%d)", p.batch, p.heads, p.len_q, p.len_k);
-    SEMIDETR_REQUIRE(p.scale == p.scale, SEMIDETR_E_BADARG, "self_attn: scale is NaN");
-    SEMIDETR_REQUIRE((int64_t)p.batch * p.heads <= 65535 && (int64_t)p.len_q * p.len_k < ((int64_t)1 << 40) &&
-                         (int64_t)p.len_q < (1 << 24) && (int64_t)p.len_k < (1 << 24) &&
-                         (int64_t)((p.len_q + 31) / 32) * ((p.len_k + 31) / 32) < ((int64_t)1 << 31) &&
-                         (int64_t)p.batch * p.heads * (p.len_q > p.len_k ? p.len_q : p.len_k) * kD < ((int64_t)1 << 40),
-                     SEMIDETR_E_TOOLARGE, "self_attn: too large (B * H <= 65535, Lq and Lk < 2^24)");
+    if (int rc = sizes_ok(p, "self_attn")) return rc;
     SEMIDETR_REQUIRE(p.q && p.k && p.v && p.out && p.lse, SEMIDETR_E_BADARG, "self_attn: null pointer (q / k / v / out / lse)");
     SEMIDETR_REQUIRE(rows_ok(p.q, p.q_stride) && rows_ok(p.k, p.k_stride) && rows_ok(p.v, p.v_stride) && aligned16(p.out),
                      SEMIDETR_E_BADARG, "self_attn: rows must be 16-byte aligned (base and strides) with non-negative strides");
@@ -377,19 +297,8 @@ int plan(const semidetr_self_attn *params, void *workspace, size_t workspace_byt
                          workspace_bytes >= semidetr_self_attn_workspace_bytes(p.batch, p.heads, p.len_q, p.len_k),
                      SEMIDETR_E_BADARG, "self_attn: workspace null, misaligned or smaller than semidetr_self_attn_workspace_bytes()");
     L.p = p;
-    L.nqt = (p.len_q + kTile - 1) / kTile;
-    L.nkt = (p.len_k + kTile - 1) / kTile;
-    L.delta = static_cast<float *>(workspace);
-    L.cls = p.mask ? reinterpret_cast<uint8_t *>(workspace) + delta_bytes(p.batch, p.heads, p.len_q) : nullptr;
+    carve(p, workspace, L, L.delta);
     return SEMIDETR_OK;
-}
-
-int launch_class(hipStream_t st, const Launch &L)
-{
-    if (!L.cls) return SEMIDETR_OK;
-    hipLaunchKernelGGL(sattn_class_kernel, dim3(L.nkt, L.nqt), dim3(64), 0, st, L.p.mask, L.p.len_q, L.p.len_k, L.nkt,
-                       const_cast<uint8_t *>(L.cls));
-    return semidetr::launch_status("sattn_class_kernel");
 }
 
 }  // namespace
@@ -406,7 +315,7 @@ extern "C" int semidetr_self_attn_forward_f32(void *stream, const semidetr_self_
     Launch L;
     if (int rc = plan(params, workspace, workspace_bytes, L, 0)) return rc;
     hipStream_t st = semidetr::as_stream(stream);
-    if (int rc = launch_class(st, L)) return rc;
+    if (int rc = launch_class(st, L, L.p.mask, L.p.len_q, L.p.len_k)) return rc;
     const dim3 grid((L.nqt + kWaves - 1) / kWaves, L.p.batch * L.p.heads);
     hipLaunchKernelGGL(sattn_q_kernel<false>, grid, dim3(kThreads), 0, st, L);
     return semidetr::launch_status("sattn_q_kernel (forward)");
@@ -418,7 +327,7 @@ extern "C" int semidetr_self_attn_backward_f32(void *stream, const semidetr_self
     Launch L;
     if (int rc = plan(params, workspace, workspace_bytes, L, 1)) return rc;
     hipStream_t st = semidetr::as_stream(stream);
-    if (int rc = launch_class(st, L)) return rc;
+    if (int rc = launch_class(st, L, L.p.mask, L.p.len_q, L.p.len_k)) return rc;
     const dim3 qgrid((L.nqt + kWaves - 1) / kWaves, L.p.batch * L.p.heads);
     hipLaunchKernelGGL(sattn_q_kernel<true>, qgrid, dim3(kThreads), 0, st, L);
     if (int rc = semidetr::launch_status("sattn_q_kernel (backward)")) return rc;

@@ -1,7 +1,7 @@
 """Decoder self-attention on the MI355X (``csrc/self_attn.hip``): the dense attention of ``DINOTransformerDecoderLayer``
 (detr_od/models/utils/transformer.py:765, 793-816), ``self.self_attn(q, k, tgt, attn_mask=self_attn_mask)[0]``.
 
-``masked_attention(q, k, v, num_heads, attn_mask=None, scale=None)`` is the core ``softmax(scale * q k^T + mask) v`` on seq-first
+``masked_attention(q, k, v, num_heads, attn_mask=None, scale=None, arithmetic="fp32")`` is the core ``softmax(scale * q k^T + mask) v`` on seq-first
 ``(L, B, E)`` tensors: forward two launches (one without a mask), backward three at most, on the current stream, with no host
 synchronisation and no ``.item()``.  The ``(Lq, Lk)`` scores never reach memory; the op saves its inputs, ``out`` and the row
 log-sum-exp ``(B, H, Lq)``.  ``q``, ``k`` and ``v`` are read through their first two strides (last stride 1, rows 16-byte
@@ -13,13 +13,22 @@ tiles are skipped.  A row with every key blocked is NaN, as in torch.
 reference ``state_dict`` loads with ``strict=True``); the two projections stay GEMMs.  ``convert_self_attention(module)``
 replaces the qualifying ``nn.MultiheadAttention`` children of a built model in place, adopting their ``Parameter`` objects.
 
-Dtypes.  ``q``, ``k`` and ``v`` may be fp32, fp16 or bf16; 16-bit operands are up-cast exactly, the arithmetic is fp32, and
-``out`` comes back in the dtype of ``q`` (of the packed ``[q | k]`` buffer), rounded once; each gradient has the dtype of its
-operand.  Under autocast the module's projections are 16-bit GEMMs, so the core receives and returns 16-bit tensors and the module
-returns what ``nn.MultiheadAttention`` returns there: a 16-bit output, fp32 gradients for fp32 inputs and parameters.
+Dtypes.  ``q``, ``k`` and ``v`` may be fp32, fp16 or bf16.  With ``arithmetic="fp32"`` (the default) 16-bit operands are up-cast
+exactly, the arithmetic is fp32, and ``out`` comes back in the dtype of ``q`` (of the packed ``[q | k]`` buffer), rounded once;
+each gradient has the dtype of its operand.  Under autocast the module's projections are 16-bit GEMMs, so the core receives and
+returns 16-bit tensors and the module returns what ``nn.MultiheadAttention`` returns there: a 16-bit output, fp32 gradients for
+fp32 inputs and parameters.
 
-Not built: float and 3-D masks, ``key_padding_mask``, attention dropout, head dimensions other than 32,
-16-bit inputs (they are computed in fp32) and the head-averaged attention weights.
+``arithmetic="operand"`` (``csrc/self_attn_h16.hip``) computes fp16 / bf16 operands of one common dtype
+on the 16-bit MFMA: the kernels read ``q``, ``k``, ``v``, ``grad_out`` and the saved ``out`` in place as 16-bit (rows 8-byte
+aligned) and write ``out`` and the gradients as 16-bit, so nothing is allocated in fp32 but ``lse`` and the workspace and no
+cast pass runs.  Its numerics contract is its own (include/semidetr_hip.h): scores, softmax statistics and ``lse`` in fp32 on the
+unrounded probabilities; ``P`` and ``dS`` rounded once to the operand type before their products; every result rounded once.
+fp32 operands take the fp32 kernels whatever ``arithmetic`` says; mixed dtypes are a ``ValueError``.  The module and
+``convert_self_attention`` carry the choice as the plain attribute ``arithmetic``.
+
+Not built: float and 3-D masks, ``key_padding_mask``, attention dropout, head dimensions other than 32
+and the head-averaged attention weights.
 """
 import ctypes
 
@@ -31,7 +40,9 @@ from torch.nn import functional as F
 from . import _lib
 
 HEAD_DIM = 32
+ARITHMETICS = ("fp32", "operand")
 _Params = _lib.SelfAttn
+_Params16 = _lib.SelfAttnH16
 
 
 def _split(x, y, z, packed_qk):
@@ -41,8 +52,8 @@ def _split(x, y, z, packed_qk):
     return x[..., :E], x[..., E:], y
 
 
-def _params(q, k, v, mask, heads, scale):
-    p = _Params()
+def _params(q, k, v, mask, heads, scale, block=_Params):
+    p = block()
     (Lq, B, E), Lk = q.shape, k.shape[0]
     p.batch, p.heads, p.head_dim, p.len_q, p.len_k, p.scale = B, heads, E // heads, Lq, Lk, scale
     _lib.set_rows(p, "q", q)
@@ -57,61 +68,104 @@ def _workspace(p, dev):
     return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
 
 
+def _operands(native, x, y, z, mask, num_heads, scale, packed_qk):
+    """q, k, v as the kernels of one arithmetic read them and their parameter block.  ``native``: the 16-bit kernels, fp16 /
+    bf16 rows in place; otherwise the fp32 kernels on exactly up-cast rows."""
+    rows = _lib.rows_native if native else _lib.rows_f32
+    q, k, v = (rows(t) for t in _split(x, y, z, packed_qk))
+    p = _params(q, k, v, mask, num_heads, scale, _Params16 if native else _Params)
+    if native:
+        p.type = _lib.row_type(q.dtype)
+    return q, k, v, p
+
+
+def _forward(ctx, native, x, y, z, mask, num_heads, scale, packed_qk):
+    q, k, v, p = _operands(native, x, y, z, mask, num_heads, scale, packed_qk)
+    dev = q.device
+    out = torch.empty(q.shape, dtype=q.dtype, device=dev)
+    lse = torch.empty((p.batch, num_heads, p.len_q), dtype=torch.float32, device=dev)
+    p.out, p.lse = out.data_ptr(), lse.data_ptr()
+    work, nbytes = _workspace(p, dev)
+    _lib.call("semidetr_self_attn_forward_h16" if native else "semidetr_self_attn_forward_f32", dev, ctypes.byref(p), work, nbytes)
+    ctx.num_heads, ctx.scale, ctx.packed_qk = num_heads, scale, packed_qk
+    ctx.dtypes = [t.dtype if t is not None else None for t in (x, y, z)]
+    ctx.save_for_backward(x, y, z, mask, out, lse)
+    return _lib.cast(out, x.dtype)
+
+
+def _backward(ctx, native, g):
+    x, y, z, mask, out, lse = ctx.saved_tensors
+    need = ctx.needs_input_grad[:3]
+    if not any(need):
+        return (None,) * 7
+    q, k, v, p = _operands(native, x, y, z, mask, ctx.num_heads, ctx.scale, ctx.packed_qk)
+    dev, dt = q.device, q.dtype                    # fp32, or the operands' 16-bit type on the native route
+    g = _lib.cast(g.detach(), dt).contiguous()
+    p.out, p.lse, p.grad_out = out.data_ptr(), lse.data_ptr(), g.data_ptr()
+    if ctx.packed_qk:
+        need_q = need_k = need[0]
+        need_v = need[1]
+        gx = torch.empty(x.shape, dtype=dt, device=dev) if need[0] else None
+        E = y.shape[2]
+        gq, gk = (gx[..., :E], gx[..., E:]) if need[0] else (None, None)
+    else:
+        need_q, need_k, need_v = need
+        gq = torch.empty(q.shape, dtype=dt, device=dev) if need_q else None
+        gk = torch.empty(k.shape, dtype=dt, device=dev) if need_k else None
+    gv = torch.empty(v.shape, dtype=dt, device=dev) if need_v else None
+    _lib.set_rows(p, "grad_q", gq, "gq_stride")
+    _lib.set_rows(p, "grad_k", gk, "gk_stride")
+    _lib.set_rows(p, "grad_v", gv, "gv_stride")
+    work, nbytes = _workspace(p, dev)
+    _lib.call("semidetr_self_attn_backward_h16" if native else "semidetr_self_attn_backward_f32", dev, ctypes.byref(p), work, nbytes)
+    if ctx.packed_qk:
+        return _lib.cast(gx, ctx.dtypes[0]), _lib.cast(gv, ctx.dtypes[1]), None, None, None, None, None
+    return _lib.cast(gq, ctx.dtypes[0]), _lib.cast(gk, ctx.dtypes[1]), _lib.cast(gv, ctx.dtypes[2]), None, None, None, None
+
+
 class MaskedAttentionFunction(torch.autograd.Function):
     """``apply(x, y, z, mask, num_heads, scale, packed_qk)`` -> ``out (Lq, B, E)``.  ``packed_qk`` false: ``x, y, z`` are
     ``q, k, v``.  True: ``x`` is the ``(L, B, 2E)`` output of one GEMM that holds ``[q | k]``, ``y`` is ``v`` and ``z`` is
     ``None``; the backward then writes ``dq`` and ``dk`` side by side into ONE gradient buffer for ``x``, so autograd adds no
-    slice-backward copies.  ``mask``: ``None`` or a contiguous ``(Lq, Lk)`` uint8 tensor, non-zero = blocked."""
+    slice-backward copies.  ``mask``: ``None`` or a contiguous ``(Lq, Lk)`` uint8 tensor, non-zero = blocked.  The fp32
+    arithmetic: 16-bit operands are up-cast exactly, every result is rounded once into its operand's dtype."""
 
     @staticmethod
-    def forward(ctx, x, y, z, mask, num_heads, scale, packed_qk):
-        q, k, v = (_lib.rows_f32(t) for t in _split(x, y, z, packed_qk))
-        dev = q.device
-        p = _params(q, k, v, mask, num_heads, scale)
-        out = torch.empty(q.shape, dtype=torch.float32, device=dev)
-        lse = torch.empty((p.batch, num_heads, p.len_q), dtype=torch.float32, device=dev)
-        p.out, p.lse = out.data_ptr(), lse.data_ptr()
-        work, nbytes = _workspace(p, dev)
-        _lib.call("semidetr_self_attn_forward_f32", dev, ctypes.byref(p), work, nbytes)
-        ctx.num_heads, ctx.scale, ctx.packed_qk = num_heads, scale, packed_qk
-        ctx.dtypes = [t.dtype if t is not None else None for t in (x, y, z)]
-        ctx.save_for_backward(x, y, z, mask, out, lse)
-        return _lib.cast(out, x.dtype)
+    def forward(ctx, *args):
+        return _forward(ctx, False, *args)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        x, y, z, mask, out, lse = ctx.saved_tensors
-        need = ctx.needs_input_grad[:3]
-        if not any(need):
-            return (None,) * 7
-        q, k, v = (_lib.rows_f32(t) for t in _split(x, y, z, ctx.packed_qk))
-        dev = q.device
-        g = g.detach()
-        if g.dtype != torch.float32:
-            g = g.float()
-        g = g.contiguous()
-        p = _params(q, k, v, mask, ctx.num_heads, ctx.scale)
-        p.out, p.lse, p.grad_out = out.data_ptr(), lse.data_ptr(), g.data_ptr()
-        if ctx.packed_qk:
-            need_q = need_k = need[0]
-            need_v = need[1]
-            gx = torch.empty(x.shape, dtype=torch.float32, device=dev) if need[0] else None
-            E = y.shape[2]
-            gq, gk = (gx[..., :E], gx[..., E:]) if need[0] else (None, None)
-        else:
-            need_q, need_k, need_v = need
-            gq = torch.empty(q.shape, dtype=torch.float32, device=dev) if need_q else None
-            gk = torch.empty(k.shape, dtype=torch.float32, device=dev) if need_k else None
-        gv = torch.empty(v.shape, dtype=torch.float32, device=dev) if need_v else None
-        _lib.set_rows(p, "grad_q", gq, "gq_stride")
-        _lib.set_rows(p, "grad_k", gk, "gk_stride")
-        _lib.set_rows(p, "grad_v", gv, "gv_stride")
-        work, nbytes = _workspace(p, dev)
-        _lib.call("semidetr_self_attn_backward_f32", dev, ctypes.byref(p), work, nbytes)
-        if ctx.packed_qk:
-            return _lib.cast(gx, ctx.dtypes[0]), _lib.cast(gv, ctx.dtypes[1]), None, None, None, None, None
-        return _lib.cast(gq, ctx.dtypes[0]), _lib.cast(gk, ctx.dtypes[1]), _lib.cast(gv, ctx.dtypes[2]), None, None, None, None
+        return _backward(ctx, False, g)
+
+
+class MaskedAttentionH16Function(torch.autograd.Function):
+    """``MaskedAttentionFunction`` with the ``operand`` arithmetic: ``x, y, z`` are fp16 or bf16 tensors of one dtype, read in
+    place (``_lib.rows_native``); ``out`` and the gradients are written in that dtype by the kernels.  Saved: the inputs, the
+    16-bit ``out`` and the fp32 ``lse``; nothing but ``lse`` and the workspace is allocated in fp32."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        return _forward(ctx, True, *args)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return _backward(ctx, True, g)
+
+
+def _function(arithmetic, *operands):
+    """The autograd function of ``arithmetic`` for these operands (``None`` entries are skipped): ``operand`` takes the 16-bit
+    kernels where the operands are fp16 or bf16, of one dtype; fp32 operands take the fp32 kernels either way."""
+    if arithmetic not in ARITHMETICS:
+        raise ValueError(f"masked_attention: arithmetic is one of {ARITHMETICS}, got {arithmetic!r}")
+    if arithmetic == "fp32":
+        return MaskedAttentionFunction
+    dtypes = {t.dtype for t in operands if t is not None}
+    if len(dtypes) != 1:
+        raise ValueError(f"masked_attention: arithmetic='operand' takes q, k and v of one dtype, got {sorted(map(str, dtypes))}")
+    return MaskedAttentionFunction if dtypes == {torch.float32} else MaskedAttentionH16Function
 
 
 def _byte_mask(attn_mask, Lq, Lk, dev):
@@ -148,13 +202,15 @@ def _check(q, k, v, num_heads):
             raise RuntimeError(f"masked_attention: {what} must live on the GPU (no CPU fallback)")
 
 
-def masked_attention(q, k, v, num_heads, attn_mask=None, scale=None):
+def masked_attention(q, k, v, num_heads, attn_mask=None, scale=None, arithmetic="fp32"):
     """``softmax(scale * q k^T + attn_mask) v`` per image and head (module docstring): ``q (Lq, B, E)``, ``k, v (Lk, B, E)`` ->
-    ``(Lq, B, E)``, ``E = num_heads * 32``.  ``scale`` defaults to ``32 ** -0.5``."""
+    ``(Lq, B, E)``, ``E = num_heads * 32``.  ``scale`` defaults to ``32 ** -0.5``.  ``arithmetic``: ``"fp32"`` or ``"operand"``
+    (fp16 / bf16 operands of one dtype on the 16-bit MFMA)."""
+    function = _function(arithmetic, q, k, v)
     mask = _byte_mask(attn_mask, q.shape[0], k.shape[0], q.device)
     _check(q, k, v, num_heads)
     scale = HEAD_DIM ** -0.5 if scale is None else float(scale)
-    return MaskedAttentionFunction.apply(q, k, v, mask, num_heads, scale, False)
+    return function.apply(q, k, v, mask, num_heads, scale, False)
 
 
 class MultiheadAttention(nn.Module):
@@ -164,11 +220,17 @@ class MultiheadAttention(nn.Module):
 
     ``forward`` returns ``(out, None)``: the reference takes ``[0]`` and never reads the head-averaged attention weights
     (transformer.py:810), so they are not computed whatever ``need_weights`` says.  With ``query is key`` (the layer's
-    ``q = k = tgt + pos``) the in-projection is one GEMM for ``[q | k]`` and one for ``v``."""
+    ``q = k = tgt + pos``) the in-projection is one GEMM for ``[q | k]`` and one for ``v``.
+
+    ``arithmetic`` (``"fp32"`` / ``"operand"``, module docstring) is a plain attribute, no parameter or buffer: ``state_dict``
+    keys are those of ``nn.MultiheadAttention``; it survives ``copy.deepcopy`` and pickling."""
+
+    arithmetic = "fp32"                     # of instances pickled before the attribute existed
 
     def __init__(self, embed_dim, num_heads, dropout=0.0, bias=True, add_bias_kv=False, add_zero_attn=False, kdim=None,
-                 vdim=None, batch_first=False):
+                 vdim=None, batch_first=False, arithmetic="fp32"):
         super().__init__()
+        self.arithmetic = _arithmetic(arithmetic)
         if add_bias_kv or add_zero_attn or batch_first:
             raise NotImplementedError("MultiheadAttention: add_bias_kv, add_zero_attn and batch_first are not built")
         if (kdim is not None and kdim != embed_dim) or (vdim is not None and vdim != embed_dim):
@@ -192,13 +254,14 @@ class MultiheadAttention(nn.Module):
             nn.init.constant_(self.out_proj.bias, 0.)
 
     @classmethod
-    def adopt(cls, mha):
+    def adopt(cls, mha, arithmetic="fp32"):
         """The mirror of a built ``nn.MultiheadAttention`` that holds the SAME ``Parameter`` objects (and ``out_proj`` module)."""
         reason = _why_not(mha)
         if reason:
             raise NotImplementedError(f"MultiheadAttention: {reason}")
         new = cls.__new__(cls)
         nn.Module.__init__(new)
+        new.arithmetic = _arithmetic(arithmetic)
         new.embed_dim, new.num_heads, new.dropout, new.head_dim = mha.embed_dim, mha.num_heads, float(mha.dropout), HEAD_DIM
         new.batch_first = False
         new.in_proj_weight = mha.in_proj_weight
@@ -209,6 +272,10 @@ class MultiheadAttention(nn.Module):
         new.out_proj = mha.out_proj
         new.train(mha.training)
         return new
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.arithmetic = _arithmetic(self.__dict__.get("arithmetic", "fp32"))
 
     def forward(self, query, key, value, attn_mask=None, need_weights=True, key_padding_mask=None):
         if key_padding_mask is not None:
@@ -222,14 +289,20 @@ class MultiheadAttention(nn.Module):
             qk = F.linear(query, W[:2 * E], None if b is None else b[:2 * E])
             v = F.linear(value, W[2 * E:], None if b is None else b[2 * E:])
             _check(qk[..., :E], qk[..., E:], v, self.num_heads)
-            out = MaskedAttentionFunction.apply(qk, v, None, mask, self.num_heads, scale, True)
+            out = _function(self.arithmetic, qk, v).apply(qk, v, None, mask, self.num_heads, scale, True)
         else:
             q = F.linear(query, W[:E], None if b is None else b[:E])
             k = F.linear(key, W[E:2 * E], None if b is None else b[E:2 * E])
             v = F.linear(value, W[2 * E:], None if b is None else b[2 * E:])
             _check(q, k, v, self.num_heads)
-            out = MaskedAttentionFunction.apply(q, k, v, mask, self.num_heads, scale, False)
+            out = _function(self.arithmetic, q, k, v).apply(q, k, v, mask, self.num_heads, scale, False)
         return self.out_proj(out), None
+
+
+def _arithmetic(name):
+    if name not in ARITHMETICS:
+        raise ValueError(f"MultiheadAttention: arithmetic is one of {ARITHMETICS}, got {name!r}")
+    return name
 
 
 def _why_not(mha):
@@ -247,14 +320,16 @@ def _why_not(mha):
     return None
 
 
-def convert_self_attention(module):
+def convert_self_attention(module, arithmetic="fp32"):
     """Replace, in place, every ``nn.MultiheadAttention`` below ``module`` that qualifies (embed_dim = 32 * heads, no dropout,
     seq-first, no bias_k / add_zero_attn) with ``MultiheadAttention.adopt`` of it: the same ``Parameter`` objects, so optimizer
-    state, EMA pairs and ``state_dict`` keys are untouched.  Returns the number converted."""
+    state, EMA pairs and ``state_dict`` keys are untouched.  ``arithmetic`` (``"fp32"`` / ``"operand"``) is set on what is
+    converted.  Returns the number converted."""
+    _arithmetic(arithmetic)
     done = 0
     for parent in list(module.modules()):
         for name, child in list(parent.named_children()):
             if type(child) is nn.MultiheadAttention and _why_not(child) is None:
-                setattr(parent, name, MultiheadAttention.adopt(child))
+                setattr(parent, name, MultiheadAttention.adopt(child, arithmetic))
                 done += 1
     return done
