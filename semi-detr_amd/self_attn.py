@@ -19,7 +19,7 @@ each gradient has the dtype of its operand.  Under autocast the module's project
 returns 16-bit tensors and the module returns what ``nn.MultiheadAttention`` returns there: a 16-bit output, fp32 gradients for
 fp32 inputs and parameters.
 
-``arithmetic="operand"`` (``csrc/self_attn_h16.hip``) computes fp16 / bf16 operands of one common dtype
+``arithmetic="operand"`` (``ArithH16`` of ``csrc/self_attn.hip``) computes fp16 / bf16 operands of one common dtype
 on the 16-bit MFMA: the kernels read ``q``, ``k``, ``v``, ``grad_out`` and the saved ``out`` in place as 16-bit (rows 8-byte
 aligned) and write ``out`` and the gradients as 16-bit, so nothing is allocated in fp32 but ``lse`` and the workspace and no
 cast pass runs.  Its numerics contract is its own (include/semidetr_hip.h): scores, softmax statistics and ``lse`` in fp32 on the

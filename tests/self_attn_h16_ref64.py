@@ -1,4 +1,4 @@
-"""The yardstick of the decoder self-attention's ``operand`` arithmetic (csrc/self_attn_h16.hip: fp16 / bf16 operands on the
+"""The yardstick of the decoder self-attention's ``operand`` arithmetic (``ArithH16`` of csrc/self_attn.hip: fp16 / bf16 operands on the
 16-bit MFMA): the float64 attention of the ROUNDED operands with a derived bound per element, and the kernel's operation order
 in numpy fp32 (``emulate``).  Test helper (not a conftest); it imports from tests/self_attn_ref64.py and modifies nothing there.
 

@@ -1,9 +1,8 @@
-"""GPU: the self-attention's ``operand`` arithmetic (csrc/self_attn_h16.hip, fp16 / bf16 operands on the 16-bit MFMA) against
+"""GPU: the self-attention's ``operand`` arithmetic (``ArithH16`` of csrc/self_attn.hip: fp16 / bf16 on the 16-bit MFMA) against
 tests/self_attn_h16_ref64.py: every element of ``out``, ``lse``, ``dq``, ``dk`` and ``dv`` of every case of
 tests/self_attn_cases.py through the C ABI, into NaN-filled buffers, in the case's own layout; gradient subsets, run-to-run
 bits, rows at 8 bytes, the memory the route holds, and the module against ``nn.MultiheadAttention`` under the same autocast."""
 import copy
-import ctypes
 
 import numpy as np
 import pytest
@@ -12,58 +11,11 @@ import torch
 import self_attn_cases as C
 import self_attn_h16_ref64 as R16
 from msda_h16_ref import torch_dtype
+from self_attn_abi import run_abi
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 WORST = {}                                   # (quantity, dtype) -> worst error / bound over the cases, printed by the last test
-
-
-def _nan(shape, dtype):
-    return torch.full(shape, float("nan"), dtype=dtype, device=DEV)
-
-
-def run_abi(p, dt, want="qkv", layout=None, grads=None, shift8=False):
-    """One forward (+ one backward for the gradients named in ``want``) through the C ABI on the operands of ``p`` rounded to
-    ``dt``, every result buffer pre-filled with NaN.  ``shift8``: q, k, v are slices whose rows start 8 bytes into a 16-byte
-    line.  -> dict of CPU tensors (``out``, ``lse``, ``dq``, ``dk``, ``dv``; an unasked gradient keeps its fill)."""
-    from semi_detr_amd import _lib, self_attn
-    tdt = torch_dtype(dt)
-    r16 = R16.rounded(p, dt)
-    q, k, v = (torch.from_numpy(r16[n]).to(DEV).to(tdt) for n in "qkv")
-    (Lq, B, E), Lk = q.shape, k.shape[0]
-    layout = layout or p["layout"]
-    packed = layout == "packed" and Lq == Lk
-    if packed:
-        buf = torch.cat([q, k, v], dim=2)
-        q, k, v = buf[..., :E], buf[..., E:2 * E], buf[..., 2 * E:]
-        gbuf = _nan((Lq, B, 3 * E), tdt)
-        gq, gk, gv = gbuf[..., :E], gbuf[..., E:2 * E], gbuf[..., 2 * E:]
-    else:
-        gq, gk, gv = _nan(q.shape, tdt), _nan(k.shape, tdt), _nan(v.shape, tdt)
-    if shift8:
-        q, k, v = (torch.cat([t.new_zeros(t.shape[0], B, 4), t], dim=2)[..., 4:] for t in (q, k, v))
-        assert all(t.data_ptr() % 16 == 8 and t.stride(0) % 4 == 0 for t in (q, k, v))
-    mask = None if p["mask"] is None else torch.from_numpy(p["mask"]).to(DEV).view(torch.uint8)
-    scale = 32 ** -0.5 if p["scale"] is None else float(p["scale"])
-    blk = self_attn._params(q, k, v, mask, p["heads"], scale, _lib.SelfAttnH16)
-    blk.type = _lib.row_type(tdt)
-    out, lse = _nan((Lq, B, E), tdt), _nan((B, p["heads"], Lq), torch.float32)
-    blk.out, blk.lse = out.data_ptr(), lse.data_ptr()
-    work, nbytes = self_attn._workspace(blk, q.device)
-    _lib.call("semidetr_self_attn_forward_h16", q.device, ctypes.byref(blk), work, nbytes)
-    got = {"out": out, "lse": lse}
-    if (grads if grads is not None else not p["forward_only"]):
-        g = torch.from_numpy(r16["gout"]).to(DEV).to(tdt)
-        blk.grad_out = g.data_ptr()
-        for n, t in (("q", gq), ("k", gk), ("v", gv)):
-            if n in want:
-                _lib.set_rows(blk, "grad_" + n, t, f"g{n}_stride")
-        work2, nbytes = self_attn._workspace(blk, q.device)
-        work2.fill_(0xFF)                    # the backward may use another workspace than the forward, uninitialised
-        _lib.call("semidetr_self_attn_backward_h16", q.device, ctypes.byref(blk), work2, nbytes)
-        got.update(dq=gq, dk=gk, dv=gv)
-    torch.cuda.synchronize()
-    return {n: t.float().cpu() for n, t in got.items()}
 
 
 def _bits(t):

@@ -76,12 +76,13 @@ def test_new_symbols_are_declared_exported_and_in_the_signature_table():
     assert lib.semidetr_abi_version() == 7
 
 
-def _block(dev_ptr=0x1000):
+def _block(dev_ptr=0x1000, fp32=False):
     """A parameter block that passes every host check but points nowhere (it is never launched: a refusal comes first)."""
     from semi_detr_amd import _lib
-    p = _lib.SelfAttnH16()
+    p = _lib.SelfAttn() if fp32 else _lib.SelfAttnH16()
     p.batch, p.heads, p.head_dim, p.len_q, p.len_k, p.scale = 1, 8, 32, 8, 8, 0.125
-    p.type = _lib.ROW_TYPES["SEMIDETR_ROW_BF16"]
+    if not fp32:
+        p.type = _lib.ROW_TYPES["SEMIDETR_ROW_BF16"]
     for n in ("q", "k", "v", "out", "lse", "grad_out", "grad_q", "grad_k", "grad_v"):
         setattr(p, n, dev_ptr)
     for n in ("q_stride", "k_stride", "v_stride", "gq_stride", "gk_stride", "gv_stride"):
@@ -128,6 +129,45 @@ def test_host_side_refusals_of_the_library_need_no_gpu():
     p = _block()
     p.grad_q = p.grad_k = p.grad_v = None
     refused(bwd, p, "no gradient asked for")
+
+
+def test_host_side_refusals_of_the_fp32_pair_need_no_gpu():
+    """The fp32 entry points go through the same host check on their widened block, with their own messages."""
+    import semi_detr_amd
+    lib = semi_detr_amd._lib.lib()
+    fwd, bwd = lib.semidetr_self_attn_forward_f32, lib.semidetr_self_attn_backward_f32
+
+    def refused(fn, p, text):
+        assert fn(None, ctypes.byref(p), None, 0) == -1, text
+        assert text.encode() in lib.semidetr_last_error(), (text, lib.semidetr_last_error())
+        assert b"self_attn_h16" not in lib.semidetr_last_error()
+    assert fwd(None, None, None, 0) == -1 and b"self_attn: null pointer (parameter block)" in lib.semidetr_last_error()
+    # a block that is refused for its missing workspace only: every other check lets it through
+    refused(fwd, _block(fp32=True), "self_attn: workspace null, misaligned or smaller than semidetr_self_attn_workspace_bytes()")
+    refused(bwd, _block(fp32=True), "self_attn: workspace null, misaligned or smaller than semidetr_self_attn_workspace_bytes()")
+    p = _block(fp32=True)
+    p.head_dim, p.heads = 64, 4
+    refused(fwd, p, "self_attn: head dimension 64 (only 32 is built)")
+    refused(bwd, p, "self_attn: head dimension 64 (only 32 is built)")
+    p = _block(0x1008, fp32=True)                             # rows 8 bytes into a 16-byte line: the 16-bit pair takes them
+    refused(fwd, p, "self_attn: rows must be 16-byte aligned (base and strides) with non-negative strides")
+    p = _block(fp32=True)
+    p.k_stride[0] = 258                                       # a leading stride that is no multiple of 4 elements
+    refused(fwd, p, "self_attn: rows must be 16-byte aligned (base and strides) with non-negative strides")
+    p = _block(fp32=True)
+    p.grad_k = 0x1008
+    refused(bwd, p, "self_attn backward: gradient rows must be 16-byte aligned (base and strides)")
+    for n in ("q", "k", "v", "out", "lse"):
+        p = _block(fp32=True)
+        setattr(p, n, None)
+        refused(fwd, p, "self_attn: null pointer (q / k / v / out / lse)")
+        refused(bwd, p, "self_attn: null pointer (q / k / v / out / lse)")
+    p = _block(fp32=True)
+    p.grad_out = None
+    refused(bwd, p, "self_attn backward: null or misaligned grad_out")
+    p = _block(fp32=True)
+    p.grad_q = p.grad_k = p.grad_v = None
+    refused(bwd, p, "self_attn backward: no gradient asked for")
 
 
 def test_arithmetic_is_checked_before_any_device_work():

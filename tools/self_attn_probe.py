@@ -11,7 +11,7 @@ GEMMs) against ``torch.nn.MultiheadAttention`` called as the reference calls it,
 
 ``--dtype fp16 | bf16`` runs every arm under ``torch.autocast`` of that type on the same fp32 inputs and weights, and times three
 arms: ``torch`` (``nn.MultiheadAttention``), ``hip`` (the mirror with ``arithmetic="fp32"``: exact up-cast, fp32 kernels) and
-``h16`` (the mirror with ``arithmetic="operand"``: csrc/self_attn_h16.hip).  ``--arithmetic fp32 | operand`` keeps only that
+``h16`` (the mirror with ``arithmetic="operand"``: the 16-bit instances of csrc/self_attn.hip).  ``--arithmetic fp32 | operand`` keeps only that
 mirror arm, for a kernel trace of its own.
 
 Shapes: Lq = 1100 with the dn mask of dn_number = 100 (a pad of 200: 100 groups of 2) and Lq = 900 without a mask, B = 4 and
