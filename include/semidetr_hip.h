@@ -287,6 +287,38 @@ int semidetr_msda_backward_h16(void *stream, int dtype, const void *grad_out, co
                                const float *attn_weight, int batch, int spatial_size, int num_heads, int channels,
                                int num_levels, int num_query, int num_point, void *workspace, void *grad_value,
                                float *grad_sampling_loc, float *grad_attn_weight);
+/* The fused MSDeformAttn prologue / epilogue (semidetr_msda_fused_forward_f32 / _backward_f32 above) on a 16-bit value map (ABI 7,
+ * additive): softmax over num_levels * num_point, location arithmetic and the padding mask inside the 16-bit kernels, so that a
+ * call under torch.autocast (or of a .half() module) reads the Linear layers' raw 16-bit outputs and no fp32 locations / weights
+ * ever exist in memory.
+ *   value, out, grad_out, grad_value            `dtype` elements (SEMIDETR_H16_FP16 / _BF16), 8-byte aligned (grad_value: 2-byte)
+ *   sampling_offsets, attn_logits and their two gradients   `prologue_type` elements: SEMIDETR_ROW_F32 (below), or the 16-bit type of
+ *                                               `dtype` (SEMIDETR_ROW_FP16 with _H16_FP16, SEMIDETR_ROW_BF16 with _H16_BF16); the other
+ *                                               16-bit type and any other code: SEMIDETR_E_BADARG.  Offsets 8-byte, logits 4-byte aligned.
+ *   reference_points                            fp32 ALWAYS, 8-byte aligned: locations are never narrowed (bf16-rounded points alone
+ *                                               leave the fp32 error bound); a 16-bit caller up-casts them, exactly
+ *   padding_mask                                (batch, spatial_size) bytes or NULL, as above; every corner tests its byte while the
+ *                                               sample records are built -- no mask_extents
+ * Contract: every result is the fp32 fused op applied to the EXACTLY up-cast operands: the softmax is computed in fp32, the location is
+ * ref + off * scale with the fp32 kernels' own code, the pixel mapping rounds as everywhere.  out, grad_value and 16-bit
+ * grad_sampling_offsets / grad_attn_logits are each rounded ONCE to nearest even from the unrounded fp32 value (an fp32 prologue_type
+ * returns the two gradients unrounded); nothing is accumulated in 16 bits.  A corner on a padded pixel is never loaded, reads as zero
+ * and receives no gradient.  `workspace`: as semidetr_msda_backward_h16 (same size function, zero-filled by the caller).
+ * Only the fast kernels exist: channels == 32, num_heads <= 32, num_levels * num_point <= 64 and the alignments above; anything else
+ * is SEMIDETR_E_BADARG (there is no generic fused kernel).  No gradient with respect to reference_points.  Both set
+ * semidetr_msda_h16_last_kernels. */
+int semidetr_msda_fused_forward_h16(void *stream, int dtype, const void *value, const int64_t *spatial_shapes,
+                                    const int64_t *level_start, const float *reference_points, int ref_dim,
+                                    const void *sampling_offsets, const void *attn_logits, int prologue_type,
+                                    const unsigned char *padding_mask, int batch, int spatial_size, int num_heads,
+                                    int channels, int num_levels, int num_query, int num_point, void *out);
+int semidetr_msda_fused_backward_h16(void *stream, int dtype, const void *grad_out, const void *value,
+                                     const int64_t *spatial_shapes, const int64_t *level_start,
+                                     const float *reference_points, int ref_dim, const void *sampling_offsets,
+                                     const void *attn_logits, int prologue_type, const unsigned char *padding_mask,
+                                     int batch, int spatial_size, int num_heads, int channels, int num_levels,
+                                     int num_query, int num_point, void *workspace, void *grad_value,
+                                     void *grad_sampling_offsets, void *grad_attn_logits);
 const char *semidetr_msda_h16_last_kernels(void);
 
 /* ---------------------------------------------------------------------------------------------

@@ -16,6 +16,11 @@ re-exports its functions; there is no Python or CPU implementation to fall back 
     ms_deform_attn_h16_backward(value16, spatial_shapes, level_start_index, sampling_loc_f32, attn_weight_f32, grad_output16
                                 [, im2col_step]) -> [grad_value (value's dtype), grad_sampling_loc (fp32), grad_attn_weight (fp32)]
     h16_supported(value, sampling_loc, attn_weight) -> the mixed-precision op takes these tensors
+    ms_deform_attn_h16_fused_forward(value16, spatial_shapes, level_start_index, reference_points, sampling_offsets, attn_logits
+                                     [, padding_mask]) -> Tensor of value's dtype; offsets / logits both value's dtype or both fp32
+    ms_deform_attn_h16_fused_backward(..., attn_logits, grad_output16[, padding_mask])
+                                -> [grad_value (value's dtype), grad_sampling_offsets, grad_attn_logits (the offsets' dtype)]
+    fused_h16_supported(value, reference_points, sampling_offsets, attn_logits) -> the fused 16-bit kernels take these tensors
     pyramid_check(spatial_shapes, level_start_index, S) -> bit 0: sum(H*W) == S, bit 1: exact tiling (cached)
     mask_extents(padding_mask, spatial_shapes, level_start_index) -> (N, L) int32 summary of a padding mask (cached; the
                                                                       fused calls fetch it themselves)
@@ -43,6 +48,9 @@ fused_supported = _msda_ext.fused_supported
 ms_deform_attn_h16_forward = _msda_ext.ms_deform_attn_h16_forward
 ms_deform_attn_h16_backward = _msda_ext.ms_deform_attn_h16_backward
 h16_supported = _msda_ext.h16_supported
+ms_deform_attn_h16_fused_forward = _msda_ext.ms_deform_attn_h16_fused_forward
+ms_deform_attn_h16_fused_backward = _msda_ext.ms_deform_attn_h16_fused_backward
+fused_h16_supported = _msda_ext.fused_h16_supported
 pyramid_check = _msda_ext.pyramid_check
 mask_extents = _msda_ext.mask_extents
 gather_choice = _msda_ext.gather_choice

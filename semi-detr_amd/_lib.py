@@ -148,6 +148,10 @@ SIGNATURES = {
     "semidetr_msda_forward_h16": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
     "semidetr_msda_backward_h16_workspace_bytes": (c_size_t, [c_int] * 4),
     "semidetr_msda_backward_h16": (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 4),
+    "semidetr_msda_fused_forward_h16": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 2 + [c_int, c_void_p] +
+                                        [c_int] * 7 + [c_void_p]),
+    "semidetr_msda_fused_backward_h16": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] + [c_void_p] * 2 + [c_int, c_void_p] +
+                                         [c_int] * 7 + [c_void_p] * 4),
     "semidetr_msda_h16_last_kernels": (ctypes.c_char_p, []),
     "semidetr_msda_set_forward_policy": (c_int, [c_int]),
     "semidetr_msda_forward_policy_state": (c_int, [c_void_p] * 4),

@@ -503,6 +503,132 @@ std::vector<at::Tensor> ms_deform_attn_fused_backward(const at::Tensor &value, c
     return {gv, go, gl};
 }
 
+// ---- the fused prologue / epilogue on a 16-bit value map (include/semidetr_hip.h: semidetr_msda_fused_forward_h16): value Half /
+// BFloat16, offsets and logits of value's dtype (what the Linear layers produce under autocast or in a .half() module) or Float,
+// reference points Float -- or value's dtype, then up-cast here, exactly (locations are never narrowed).
+bool is_h16(const at::Tensor &t) { return t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16; }
+bool aligned_to(const at::Tensor &t, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & (bytes - 1)) == 0; }
+
+bool fused_h16_supported(const at::Tensor &value, const at::Tensor &ref, const at::Tensor &off, const at::Tensor &logits)
+{
+    if (!(value.is_cuda() && is_h16(value) && value.dim() == 4 && value.size(3) == 32 && value.size(2) <= 32)) return false;
+    if (!(ref.dim() == 4 && (ref.size(-1) == 2 || ref.size(-1) == 4) && off.dim() == 6 && logits.dim() == 4)) return false;
+    if (!(ref.scalar_type() == at::kFloat || ref.scalar_type() == value.scalar_type())) return false;
+    if (off.scalar_type() != logits.scalar_type() || !(off.scalar_type() == at::kFloat || off.scalar_type() == value.scalar_type()))
+        return false;
+    if (off.size(3) > 32 || off.size(3) * off.size(4) > 64) return false;
+    // (a tensor that is not contiguous is made so by the caller: its copy is a fresh, aligned allocation)
+    return (!value.is_contiguous() || aligned_to(value, 8)) && (!off.is_contiguous() || aligned_to(off, 8)) &&
+           (!logits.is_contiguous() || aligned_to(logits, 4));
+}
+
+Dims fused_h16_dims(const at::Tensor &value, const at::Tensor &shapes, const at::Tensor &starts, const at::Tensor &ref,
+                    const at::Tensor &off, const at::Tensor &logits, const char *what)
+{
+    TORCH_CHECK(value.is_cuda(), "Not implemented on the CPU");
+    check_tensor(value, value, "value");
+    check_tensor(shapes, value, "spatial_shapes");
+    check_tensor(starts, value, "level_start_index");
+    check_tensor(ref, value, "reference_points");
+    check_tensor(off, value, "sampling_offsets");
+    check_tensor(logits, value, "attention logits");
+    TORCH_CHECK(shapes.scalar_type() == at::kLong && starts.scalar_type() == at::kLong,
+                "expected scalar type Long for spatial_shapes / level_start_index");
+    TORCH_CHECK(value.dim() == 4 && off.dim() == 6 && logits.dim() == 4 && ref.dim() == 4, what,
+                ": expected value (N,S,M,D), sampling_offsets (N,Lq,M,L,P,2), logits (N,Lq,M,L*P), reference (N,Lq,L,2|4)");
+    TORCH_CHECK(is_h16(value), what, ": value must be Half or BFloat16, got '", scalar_name(value.scalar_type()),
+                "' -- the fp32 entry is ms_deform_attn_fused_forward / ms_deform_attn_fused_backward");
+    TORCH_CHECK(off.scalar_type() == logits.scalar_type() && (off.scalar_type() == at::kFloat || off.scalar_type() == value.scalar_type()),
+                what, ": sampling_offsets and attention logits must both be Float or both be value's dtype ('",
+                scalar_name(value.scalar_type()), "'), got '", scalar_name(off.scalar_type()), "' and '",
+                scalar_name(logits.scalar_type()), "'");
+    TORCH_CHECK(ref.scalar_type() == at::kFloat || ref.scalar_type() == value.scalar_type(), what,
+                ": reference_points must be Float or value's dtype, got '", scalar_name(ref.scalar_type()), "'");
+    Dims d;
+    d.N = (int)value.size(0); d.S = (int)value.size(1); d.M = (int)value.size(2); d.D = (int)value.size(3);
+    d.Lq = (int)off.size(1); d.L = (int)off.size(3); d.P = (int)off.size(4);
+    TORCH_CHECK(off.size(0) == d.N && off.size(2) == d.M && off.size(5) == 2 && logits.size(0) == d.N &&
+                    logits.size(1) == d.Lq && logits.size(2) == d.M && logits.size(3) == (int64_t)d.L * d.P &&
+                    ref.size(0) == d.N && ref.size(1) == d.Lq && ref.size(2) == d.L && shapes.dim() == 2 && shapes.size(0) == d.L &&
+                    shapes.size(1) == 2 && starts.numel() == d.L,
+                what, ": inconsistent tensor shapes");
+    if (ref.size(-1) != 2 && ref.size(-1) != 4)
+        throw py::value_error("Last dim of reference_points must be 2 or 4, but get " + std::to_string(ref.size(-1)) +
+                              " instead.");
+    TORCH_CHECK(d.D == 32 && d.M <= 32, what, ": the fused 16-bit kernels take 32 channels per head and at most 32 heads (got ", d.D,
+                " and ", d.M, "); there is no generic fused kernel -- see fused_h16_supported");
+    TORCH_CHECK(aligned_to(value, 8) && aligned_to(off, 8) && aligned_to(logits, 4), what,
+                ": value and sampling_offsets must be 8-byte aligned, attention logits 4-byte aligned");
+    return d;
+}
+
+int prologue_type_of(const at::Tensor &off)
+{
+    return off.scalar_type() == at::kFloat ? SEMIDETR_ROW_F32 : (off.scalar_type() == at::kHalf ? SEMIDETR_ROW_FP16 : SEMIDETR_ROW_BF16);
+}
+
+// fp32 reference points in 8-byte aligned storage: an exact up-cast of 16-bit points (small: N * Lq * L * 2|4 numbers)
+at::Tensor ref_f32(const at::Tensor &ref)
+{
+    const at::Tensor r = ref.scalar_type() == at::kFloat ? ref : ref.to(at::kFloat);
+    return aligned_to(r, 8) ? r : r.clone();
+}
+
+at::Tensor ms_deform_attn_h16_fused_forward(const at::Tensor &value, const at::Tensor &spatial_shapes,
+                                            const at::Tensor &level_start_index, const at::Tensor &reference_points,
+                                            const at::Tensor &sampling_offsets, const at::Tensor &attn_logits,
+                                            const c10::optional<at::Tensor> &padding_mask)
+{
+    const char *what = "ms_deform_attn_h16_fused_forward";
+    const Dims d = fused_h16_dims(value, spatial_shapes, level_start_index, reference_points, sampling_offsets, attn_logits, what);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
+    at::Tensor out = at::empty({d.N, d.Lq, (int64_t)d.M * d.D}, value.options());      // the kernel writes all of it
+    if (out.numel() == 0 || value.numel() == 0) return out.zero_();
+    // the kernels index the mask and the value map through the level table: it has to describe exactly S pixels
+    TORCH_CHECK((pyramid_check(spatial_shapes, level_start_index, d.S) & 1) != 0, what,
+                ": sum(H * W) of spatial_shapes must equal value.size(1)");
+    const at::Tensor ref = ref_f32(reference_points);
+    const int rc = semidetr_msda_fused_forward_h16(
+        stream_of(value), h16_dtype(value), value.data_ptr(), spatial_shapes.data_ptr<int64_t>(), level_start_index.data_ptr<int64_t>(),
+        ref.data_ptr<float>(), (int)ref.size(-1), sampling_offsets.data_ptr(), attn_logits.data_ptr(), prologue_type_of(sampling_offsets),
+        mask_ptr(padding_mask, value, d), d.N, d.S, d.M, d.D, d.L, d.Lq, d.P, out.data_ptr());
+    check_rc(rc, what);
+    return out;
+}
+
+std::vector<at::Tensor> ms_deform_attn_h16_fused_backward(const at::Tensor &value, const at::Tensor &spatial_shapes,
+                                                          const at::Tensor &level_start_index, const at::Tensor &reference_points,
+                                                          const at::Tensor &sampling_offsets, const at::Tensor &attn_logits,
+                                                          const at::Tensor &grad_output,
+                                                          const c10::optional<at::Tensor> &padding_mask)
+{
+    const char *what = "ms_deform_attn_h16_fused_backward";
+    const Dims d = fused_h16_dims(value, spatial_shapes, level_start_index, reference_points, sampling_offsets, attn_logits, what);
+    check_tensor(grad_output, value, "grad_output");
+    TORCH_CHECK(grad_output.scalar_type() == value.scalar_type(), what, ": value ('", scalar_name(value.scalar_type()),
+                "') and grad_output ('", scalar_name(grad_output.scalar_type()), "') must share one dtype");
+    TORCH_CHECK(grad_output.numel() == (int64_t)d.N * d.Lq * d.M * d.D && aligned_to(grad_output, 8), what,
+                ": grad_output must be (N, Lq, M*D), 8-byte aligned");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
+    at::Tensor gv = at::empty_like(value);      // every element written by the conversion kernel
+    at::Tensor go = at::empty_like(sampling_offsets), gl = at::empty_like(attn_logits);      // fully written by the kernel
+    if (value.numel() == 0 || go.numel() == 0) return {gv.zero_(), go.zero_(), gl.zero_()};
+    TORCH_CHECK((pyramid_check(spatial_shapes, level_start_index, d.S) & 1) != 0, what,
+                ": sum(H * W) of spatial_shapes must equal value.size(1)");
+    const at::Tensor ref = ref_f32(reference_points);
+    // grad_value is summed in fp32 and rounded once: the sums live in this workspace, cleared on the current stream
+    at::Tensor ws = at::empty({(int64_t)(semidetr_msda_backward_h16_workspace_bytes(d.N, d.S, d.M, d.D) / sizeof(float))},
+                              value.options().dtype(at::kFloat));
+    ws.zero_();
+    const int rc = semidetr_msda_fused_backward_h16(
+        stream_of(value), h16_dtype(value), grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr<int64_t>(),
+        level_start_index.data_ptr<int64_t>(), ref.data_ptr<float>(), (int)ref.size(-1), sampling_offsets.data_ptr(),
+        attn_logits.data_ptr(), prologue_type_of(sampling_offsets), mask_ptr(padding_mask, value, d), d.N, d.S, d.M, d.D, d.L, d.Lq,
+        d.P, ws.data_ptr(), gv.data_ptr(), go.data_ptr(), gl.data_ptr());
+    check_rc(rc, what);
+    return {gv, go, gl};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -532,6 +658,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("im2col_step") = 64);
     m.def("h16_supported", &h16_supported, py::arg("value"), py::arg("sampling_loc"), py::arg("attn_weight"),
           "value is a 16-bit (Half / BFloat16) CUDA map and locations / weights are Float: the mixed-precision op takes the call");
+    // ... and with the fused prologue / epilogue inside those kernels (semidetr_msda_fused_forward_h16)
+    m.def("ms_deform_attn_h16_fused_forward", &ms_deform_attn_h16_fused_forward, py::arg("value"), py::arg("spatial_shapes"),
+          py::arg("level_start_index"), py::arg("reference_points"), py::arg("sampling_offsets"), py::arg("attn_logits"),
+          py::arg("padding_mask") = py::none());
+    m.def("ms_deform_attn_h16_fused_backward", &ms_deform_attn_h16_fused_backward, py::arg("value"), py::arg("spatial_shapes"),
+          py::arg("level_start_index"), py::arg("reference_points"), py::arg("sampling_offsets"), py::arg("attn_logits"),
+          py::arg("grad_output"), py::arg("padding_mask") = py::none());
+    m.def("fused_h16_supported", &fused_h16_supported, py::arg("value"), py::arg("reference_points"), py::arg("sampling_offsets"),
+          py::arg("attn_logits"),
+          "value is a 16-bit CUDA map of 32 channels per head, offsets / logits are both Float or both value's dtype, reference points "
+          "Float or value's dtype: the fused 16-bit kernels take the call");
     m.def("gather_choice", [](int64_t slot) { return semidetr_msda_gather_choice((int)slot); }, py::arg("policy_slot") = 0,
           "What an encoder backward of this slot issued now would pick for grad_sampling_loc / grad_attn_weight (SEMIDETR_MSDA_GATHER_WINDOW "
           "or _PATCH): OR it into the backward call's policy_slot and the backward follows what was known at forward time.");

@@ -12,9 +12,7 @@
 // layers) and do the softmax over L*P and the location arithmetic themselves, so the (N,Lq,M,L,P[,2])
 // intermediates (and their backward) never touch HBM.
 // ---------------------------------------------------------------------------------------------
-// 1 / x as ONE v_rcp_f32 (1 ulp).  __frcp_rn is the correctly rounded reciprocal -- on gfx950 the full IEEE division
-// sequence (v_div_scale / v_rcp / 4 fma / v_div_fmas / v_div_fixup), ten instructions where the fused prologue wants one.
-__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+// (fast_rcp -- 1 / x as one v_rcp_f32 -- and the prologue's location arithmetic are msda_geom.h's)
 
 // Streaming (non-temporal) accesses for data that is read or written exactly ONCE per launch -- sampling locations, attention
 // weights / logits, the op's outputs: the lines are not kept in the caches, so they stop displacing the value rows every
@@ -229,13 +227,7 @@ struct RawIO {
     }
     __device__ __forceinline__ void finish_xy(const float2 o, const float4 r, int P, int H, int W, float &x, float &y) const
     {
-        // x / W as x * rcp(W) (v_rcp_f32, 1 ulp): a true division is ~10 instructions per coordinate, and the location is
-        // compared with the reference's to 1e-4, not bit for bit (the oracle-exact path is LocAttnIO)
-        const bool box = ref_dim == 4;               // ms_deform_attn.py:106-108 (boxes) vs :102-105 (points)
-        const float ip = 0.5f * fast_rcp((float)P);
-        const float sx = box ? ip * r.z : fast_rcp((float)W), sy = box ? ip * r.w : fast_rcp((float)H);
-        x = r.x + o.x * sx;
-        y = r.y + o.y * sy;
+        fused_loc_xy(o, r, ref_dim, P, H, W, x, y);      // msda_geom.h: the 16-bit kernels (msda_h16.hip) form it with the same code
     }
     // Round 6, the window kernels' form.  Their queries are pixels, whose reference points are 2-d in every DETR encoder
     // (transformer.py:675-691): the prefetched data is the offset and the 8-byte point -- not the 16-byte box, two registers per

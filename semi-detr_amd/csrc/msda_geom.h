@@ -77,6 +77,31 @@ __device__ __forceinline__ bool sample_setup_oob(float x, float y, int H, int W,
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------
+// location arithmetic of the fused MSDeformAttn prologue (ms_deform_attn.py:102-108), shared by the fp32 kernels' RawIO
+// (msda_fast.h) and the 16-bit kernels (msda_h16.hip): loc = ref + off * scale, per coordinate
+// ---------------------------------------------------------------------------------------------
+// 1 / x as ONE v_rcp_f32 (1 ulp).  __frcp_rn is the correctly rounded reciprocal -- on gfx950 the full IEEE division
+// sequence (v_div_scale / v_rcp / 4 fma / v_div_fmas / v_div_fixup), ten instructions where the fused prologue wants one.
+__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+
+// scale = d loc / d offset: (1 / W, 1 / H) for 2-d points (:102-105), 0.5 / P x the box's (w, h) = r.zw for 4-d boxes (:106-108).
+// x / W as x * rcp(W) (v_rcp_f32, 1 ulp): a true division is ~10 instructions per coordinate, and the location is
+// compared with the reference's to 1e-4, not bit for bit (the oracle-exact path is LocAttnIO)
+__device__ __forceinline__ float2 fused_loc_scale(const float4 r, int ref_dim, int P, int H, int W)
+{
+    const bool box = ref_dim == 4;
+    const float ip = 0.5f * fast_rcp((float)P);
+    return make_float2(box ? ip * r.z : fast_rcp((float)W), box ? ip * r.w : fast_rcp((float)H));
+}
+// o: the raw offset, r: the reference point {x, y[, w, h]}
+__device__ __forceinline__ void fused_loc_xy(const float2 o, const float4 r, int ref_dim, int P, int H, int W, float &x, float &y)
+{
+    const float2 s = fused_loc_scale(r, ref_dim, P, H, W);
+    x = r.x + o.x * s.x;
+    y = r.y + o.y * s.y;
+}
+
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const float *image_base, unsigned image_bytes)
 {
     // The descriptor is wave-uniform (it depends on blockIdx only) but the compiler cannot prove it and would

@@ -22,6 +22,12 @@
 //                                   channel sums for grad_attn / grad_loc by DPP inside the half-wave, staged in LDS.
 //  * msda_h16_convert<T16>          fp32 workspace -> 16-bit grad_value, 8 elements (one 16-byte store) per thread.
 //  * msda_{fwd,bwd}_h16_generic<T16> any D, any head count, any alignment: one wavefront per (n, q, m) row, lane per channel.
+//  * msda_fwd_h16_fused<T16, PT, SPLIT>, msda_bwd_h16_fused<T16, PT>: the two fast kernels with the MSDeformAttn prologue / epilogue
+//                                   inside (semidetr_msda_fused_{forward,backward}_h16): the sample records come from the fp32
+//                                   reference points, the RAW offsets and logits (PT = float | T16) and the padding mask bytes;
+//                                   softmax over L * P and ref + off * scale (msda_geom.h fused_loc_xy, the fp32 kernels' code) in
+//                                   fp32; the backward's write-back applies the softmax backward and the offset scale and rounds a
+//                                   16-bit PT once.  The gather / row phases are the SAME device functions as the unfused kernels'.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
@@ -79,6 +85,51 @@ __device__ __forceinline__ Tile tile_of_block(int M, int tiles_per_image, int ro
     return t;
 }
 
+// Phase 2 of the D == 32 forwards (msda_fwd_h16, msda_fwd_h16_fused): gather + weighted sum in fp32 from the tile's LDS records,
+// one 8-byte non-temporal store per lane.
+template <typename T16, int SPLIT>
+__device__ __forceinline__ void fwd_gather_store(const T16 *__restrict__ value, const int4 *rec_off, const float4 *rec_w, const Tile t,
+                                                 int S, int M, int LP, int LPP, int Lq, T16 *__restrict__ out)
+{
+    const int g = threadIdx.x >> 3, j = threadIdx.x & 7;
+    const int r = g / SPLIT, part = g % SPLIT;
+    const int q = t.q0 + r;
+    // value slice of image n as a raw buffer of exactly S * M * D * 2 bytes: kOob (invalid corners) reads as zero
+    const __amdgpu_buffer_rsrc_t vr = image_rsrc(reinterpret_cast<const float *>(value + (int64_t)t.n * S * M * kD),
+                                                 (unsigned)S * M * kD * 2u);
+    const unsigned lane_b = (unsigned)(t.m * kD + 4 * j) * 2u;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int4 *ro = rec_off + r * LPP;
+    const float4 *rw = rec_w + r * LPP;
+#pragma unroll 4
+    for (int k = part; k < LP; k += SPLIT) {
+        const int4 o = ro[k];
+        const float4 w = rw[k];
+        const float4 v1 = unpack4<T16>(buf_ld2(vr, (unsigned)o.x + lane_b)), v2 = unpack4<T16>(buf_ld2(vr, (unsigned)o.y + lane_b));
+        const float4 v3 = unpack4<T16>(buf_ld2(vr, (unsigned)o.z + lane_b)), v4 = unpack4<T16>(buf_ld2(vr, (unsigned)o.w + lane_b));
+        acc.x += w.x * v1.x + w.y * v2.x + w.z * v3.x + w.w * v4.x;
+        acc.y += w.x * v1.y + w.y * v2.y + w.z * v3.y + w.w * v4.y;
+        acc.z += w.x * v1.z + w.y * v2.z + w.z * v3.z + w.w * v4.z;
+        acc.w += w.x * v1.w + w.y * v2.w + w.z * v3.w + w.w * v4.w;
+    }
+    if (SPLIT > 1) {
+#pragma unroll
+        for (int s = 8; s < 8 * SPLIT; s <<= 1) {
+            acc.x += __shfl_xor(acc.x, s, 64);
+            acc.y += __shfl_xor(acc.y, s, 64);
+            acc.z += __shfl_xor(acc.z, s, 64);
+            acc.w += __shfl_xor(acc.w, s, 64);
+        }
+    }
+    if (part == 0 && q < Lq) {      // every row is written, a row without a sample on the map as zeros (`out` is not pre-cleared)
+        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
+        u32x2 pk;
+        pk.x = pack2<T16>(acc.x, acc.y);
+        pk.y = pack2<T16>(acc.z, acc.w);
+        __builtin_nontemporal_store(pk, reinterpret_cast<u32x2 *>(out + row * kD + 4 * j));
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // forward, D == 32.  SPLIT = number of 8-lane groups that share one query row (each takes samples part, part + SPLIT, ...):
 // small query sets still fill the chip.  LDS: (32 / SPLIT) x (L * P + 1) records of 32 bytes.
@@ -121,42 +172,53 @@ __global__ __launch_bounds__(256) void msda_fwd_h16(const T16 *__restrict__ valu
     __syncthreads();
 
     // ---- phase 2: gather + weighted sum in fp32
-    const int g = threadIdx.x >> 3, j = threadIdx.x & 7;
-    const int r = g / SPLIT, part = g % SPLIT;
-    const int q = t.q0 + r;
-    // value slice of image n as a raw buffer of exactly S * M * D * 2 bytes: kOob (invalid corners) reads as zero
+    fwd_gather_store<T16, SPLIT>(value, rec_off, rec_w, t, S, M, LP, LPP, Lq, out);
+}
+
+// Row phase of the D == 32 backwards (msda_bwd_h16, msda_bwd_h16_fused): each half-wave walks its rows' LDS records {corner
+// offsets} / {lw, lh, a, level}: fp32 atomics into the workspace, and the record overwritten with {g_attn, g_x, g_y, a}.
+template <typename T16>
+__device__ __forceinline__ void bwd_rows(const T16 *__restrict__ gout, const T16 *__restrict__ value, const int4 *rec_off,
+                                         float4 *rec_p, const float *lev_w, const float *lev_h, const Tile t, int S, int M, int LP,
+                                         int LPP, int Lq, int rpb, float *__restrict__ gws)
+{
+    const int hw = threadIdx.x >> 5, c = threadIdx.x & 31;      // half-wave index, channel
     const __amdgpu_buffer_rsrc_t vr = image_rsrc(reinterpret_cast<const float *>(value + (int64_t)t.n * S * M * kD),
                                                  (unsigned)S * M * kD * 2u);
-    const unsigned lane_b = (unsigned)(t.m * kD + 4 * j) * 2u;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int4 *ro = rec_off + r * LPP;
-    const float4 *rw = rec_w + r * LPP;
-#pragma unroll 4
-    for (int k = part; k < LP; k += SPLIT) {
-        const int4 o = ro[k];
-        const float4 w = rw[k];
-        const float4 v1 = unpack4<T16>(buf_ld2(vr, (unsigned)o.x + lane_b)), v2 = unpack4<T16>(buf_ld2(vr, (unsigned)o.y + lane_b));
-        const float4 v3 = unpack4<T16>(buf_ld2(vr, (unsigned)o.z + lane_b)), v4 = unpack4<T16>(buf_ld2(vr, (unsigned)o.w + lane_b));
-        acc.x += w.x * v1.x + w.y * v2.x + w.z * v3.x + w.w * v4.x;
-        acc.y += w.x * v1.y + w.y * v2.y + w.z * v3.y + w.w * v4.y;
-        acc.z += w.x * v1.z + w.y * v2.z + w.z * v3.z + w.w * v4.z;
-        acc.w += w.x * v1.w + w.y * v2.w + w.z * v3.w + w.w * v4.w;
-    }
-    if (SPLIT > 1) {
-#pragma unroll
-        for (int s = 8; s < 8 * SPLIT; s <<= 1) {
-            acc.x += __shfl_xor(acc.x, s, 64);
-            acc.y += __shfl_xor(acc.y, s, 64);
-            acc.z += __shfl_xor(acc.z, s, 64);
-            acc.w += __shfl_xor(acc.w, s, 64);
-        }
-    }
-    if (part == 0 && q < Lq) {      // every row is written, a row without a sample on the map as zeros (`out` is not pre-cleared)
+    const unsigned lane_b = (unsigned)(t.m * kD + c) * 2u;
+    float *gvb = gws + (int64_t)t.n * S * M * kD + t.m * kD + c;      // + corner byte offset / 2
+    for (int r = hw; r < rpb; r += 8) {
+        const int q = t.q0 + r;
+        if (q >= Lq) break;
         const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
-        u32x2 pk;
-        pk.x = pack2<T16>(acc.x, acc.y);
-        pk.y = pack2<T16>(acc.z, acc.w);
-        __builtin_nontemporal_store(pk, reinterpret_cast<u32x2 *>(out + row * kD + 4 * j));
+        const float go = ld16(gout + row * kD + c);
+        const int4 *ro = rec_off + r * LPP;
+        float4 *rp = rec_p + r * LPP;
+#pragma unroll 4
+        for (int k = 0; k < LP; ++k) {
+            const int4 o = ro[k];
+            const float4 pr = rp[k];
+            const float lw = pr.x, lh = pr.y, a = pr.z;
+            const int l = __float_as_int(pr.w);
+            const float hh = 1.f - lh, hwt = 1.f - lw;
+            const float ga = go * a;
+            // d_i = grad_out[c] * v_i[c]; corners outside the level read as zero (buffer bounds check)
+            const float d1 = go * Cvt<T16>::up((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(vr, (unsigned)o.x + lane_b, 0, 0));
+            const float d2 = go * Cvt<T16>::up((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(vr, (unsigned)o.y + lane_b, 0, 0));
+            const float d3 = go * Cvt<T16>::up((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(vr, (unsigned)o.z + lane_b, 0, 0));
+            const float d4 = go * Cvt<T16>::up((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(vr, (unsigned)o.w + lane_b, 0, 0));
+            if ((unsigned)o.x != kOob) unsafeAtomicAdd(gvb + ((unsigned)o.x >> 1), hh * hwt * ga);
+            if ((unsigned)o.y != kOob) unsafeAtomicAdd(gvb + ((unsigned)o.y >> 1), hh * lw * ga);
+            if ((unsigned)o.z != kOob) unsafeAtomicAdd(gvb + ((unsigned)o.z >> 1), lh * hwt * ga);
+            if ((unsigned)o.w != kOob) unsafeAtomicAdd(gvb + ((unsigned)o.w >> 1), lh * lw * ga);
+            float pa = hh * hwt * d1 + hh * lw * d2 + lh * hwt * d3 + lh * lw * d4;
+            float px = a * (hh * (d2 - d1) + lh * (d4 - d3));
+            float py = a * (hwt * (d3 - d1) + lw * (d4 - d2));
+            pa = half32_sum(pa);
+            px = half32_sum(px);
+            py = half32_sum(py);
+            if (c == 16) rp[k] = make_float4(pa, lev_w[l] * px, lev_h[l] * py, a);
+        }
     }
 }
 
@@ -205,44 +267,7 @@ __global__ __launch_bounds__(256) void msda_bwd_h16(const T16 *__restrict__ gout
     }
     __syncthreads();
 
-    const int hw = threadIdx.x >> 5, c = threadIdx.x & 31;      // half-wave index, channel
-    const __amdgpu_buffer_rsrc_t vr = image_rsrc(reinterpret_cast<const float *>(value + (int64_t)t.n * S * M * kD),
-                                                 (unsigned)S * M * kD * 2u);
-    const unsigned lane_b = (unsigned)(t.m * kD + c) * 2u;
-    float *gvb = gws + (int64_t)t.n * S * M * kD + t.m * kD + c;      // + corner byte offset / 2
-    for (int r = hw; r < rpb; r += 8) {
-        const int q = t.q0 + r;
-        if (q >= Lq) break;
-        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
-        const float go = ld16(gout + row * kD + c);
-        const int4 *ro = rec_off + r * LPP;
-        float4 *rp = rec_p + r * LPP;
-#pragma unroll 4
-        for (int k = 0; k < LP; ++k) {
-            const int4 o = ro[k];
-            const float4 pr = rp[k];
-            const float lw = pr.x, lh = pr.y, a = pr.z;
-            const int l = __float_as_int(pr.w);
-            const float hh = 1.f - lh, hwt = 1.f - lw;
-            const float ga = go * a;
-            // d_i = grad_out[c] * v_i[c]; corners outside the level read as zero (buffer bounds check)
-            const float d1 = go * Cvt<T16>::up((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(vr, (unsigned)o.x + lane_b, 0, 0));
-            const float d2 = go * Cvt<T16>::up((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(vr, (unsigned)o.y + lane_b, 0, 0));
-            const float d3 = go * Cvt<T16>::up((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(vr, (unsigned)o.z + lane_b, 0, 0));
-            const float d4 = go * Cvt<T16>::up((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(vr, (unsigned)o.w + lane_b, 0, 0));
-            if ((unsigned)o.x != kOob) unsafeAtomicAdd(gvb + ((unsigned)o.x >> 1), hh * hwt * ga);
-            if ((unsigned)o.y != kOob) unsafeAtomicAdd(gvb + ((unsigned)o.y >> 1), hh * lw * ga);
-            if ((unsigned)o.z != kOob) unsafeAtomicAdd(gvb + ((unsigned)o.z >> 1), lh * hwt * ga);
-            if ((unsigned)o.w != kOob) unsafeAtomicAdd(gvb + ((unsigned)o.w >> 1), lh * lw * ga);
-            float pa = hh * hwt * d1 + hh * lw * d2 + lh * hwt * d3 + lh * lw * d4;
-            float px = a * (hh * (d2 - d1) + lh * (d4 - d3));
-            float py = a * (hwt * (d3 - d1) + lw * (d4 - d2));
-            pa = half32_sum(pa);
-            px = half32_sum(px);
-            py = half32_sum(py);
-            if (c == 16) rp[k] = make_float4(pa, lev_w[l] * px, lev_h[l] * py, a);
-        }
-    }
+    bwd_rows<T16>(gout, value, rec_off, rec_p, lev_w, lev_h, t, S, M, LP, LPP, Lq, rpb, gws);
     __syncthreads();
 
     // ---- coalesced write-back of grad_attn_weight / grad_sampling_loc (fp32, unrounded)
@@ -276,6 +301,246 @@ __global__ __launch_bounds__(256) void msda_h16_convert(const float *__restrict_
     }
     const int64_t end = i + 8 < count ? i + 8 : count;
     for (int64_t e = i; e < end; ++e) st16(dst + e, ws[e]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Fused prologue / epilogue on a 16-bit value map: the kernels above with the sample records built from the
+// fp32 reference points, the RAW sampling offsets and the RAW attention logits, and the padding mask as bytes -- what RawIO
+// (msda_fast.h) is to the fp32 kernels.  Offsets, logits and their gradients are PT = float or T16 (the C ABI's prologue_type);
+// the softmax, the locations and every sum are fp32.
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename PT>
+struct Prologue {
+    const float *ref;               // (N, Lq, L, ref_dim), fp32 always: locations are never narrowed
+    const PT *off, *logit;          // (N, Lq, M, L, P, 2), (N, Lq, M, L * P)
+    const unsigned char *mask;      // (N, S) bytes, nonzero = padded pixel, or null
+    int ref_dim;
+};
+// element access of the raw operands: a 16-bit offset pair is one dword (x in the low half)
+template <typename PT>
+struct RawOp {
+    static __device__ __forceinline__ float2 ld_off(const PT *p, int64_t i)
+    {
+        const unsigned b = *reinterpret_cast<const unsigned *>(p + 2 * i);
+        return make_float2(Cvt<PT>::up(b & 0xffffu), Cvt<PT>::up(b >> 16));
+    }
+    static __device__ __forceinline__ float ld_logit(const PT *p, int64_t i) { return ld16(p + i); }
+    static __device__ __forceinline__ void st_off(PT *p, int64_t i, float2 v) { *reinterpret_cast<unsigned *>(p + 2 * i) = pack2<PT>(v.x, v.y); }
+    static __device__ __forceinline__ void st_logit(PT *p, int64_t i, float v) { st16(p + i, v); }
+};
+template <>
+struct RawOp<float> {
+    static __device__ __forceinline__ float2 ld_off(const float *p, int64_t i) { return *reinterpret_cast<const float2 *>(p + 2 * i); }
+    static __device__ __forceinline__ float ld_logit(const float *p, int64_t i) { return p[i]; }
+    static __device__ __forceinline__ void st_off(float *p, int64_t i, float2 v) { *reinterpret_cast<float2 *>(p + 2 * i) = v; }
+    static __device__ __forceinline__ void st_logit(float *p, int64_t i, float v) { p[i] = v; }
+};
+
+// Reductions over a lane-aligned group of LP threads, LP a power of two <= 64 (msda_fast.h lp_group_max / lp_group_sum: DPP inside
+// a 16-lane row, shuffles beyond); every lane of the group gets the result.
+__device__ __forceinline__ bool lp_shuffles(int LP) { return (LP & (LP - 1)) == 0 && LP <= 64; }
+__device__ __forceinline__ float lp_group_sum(float x, int LP)
+{
+    if (LP >= 2) x += dpp_mov<0xB1>(x);
+    if (LP >= 4) x += dpp_mov<0x4E>(x);
+    if (LP >= 8) x += dpp_mov<0x141>(x);
+    if (LP >= 16) x += dpp_mov<0x140>(x);
+    if (LP >= 32) x += __shfl_xor(x, 16, 64);
+    if (LP >= 64) x += __shfl_xor(x, 32, 64);
+    return x;
+}
+__device__ __forceinline__ float lp_group_max(float x, int LP)
+{
+    if (LP >= 2) x = fmaxf(x, dpp_mov<0xB1>(x));
+    if (LP >= 4) x = fmaxf(x, dpp_mov<0x4E>(x));
+    if (LP >= 8) x = fmaxf(x, dpp_mov<0x141>(x));
+    if (LP >= 16) x = fmaxf(x, dpp_mov<0x140>(x));
+    if (LP >= 32) x = fmaxf(x, __shfl_xor(x, 16, 64));
+    if (LP >= 64) x = fmaxf(x, __shfl_xor(x, 32, 64));
+    return x;
+}
+
+// The reference point of (query, level) as {x, y, w, h}: one 8-byte buffer load for a point, two for a box -- branch-free: a
+// point's second load is sent out of range and returns zeros.  `rr` covers the image's Lq * L * ref_dim floats.
+__device__ __forceinline__ float4 ld_ref(__amdgpu_buffer_rsrc_t rr, int ql, int ref_dim)
+{
+    const unsigned b = (unsigned)(ql * ref_dim) * 4u;
+    const float2 c = buf_ld2(rr, b), wh = buf_ld2(rr, ref_dim == 4 ? b + 8u : kOob);
+    return make_float4(c.x, c.y, wh.x, wh.y);
+}
+
+// exp(logit - row max) of every sample of the tile into LDS, for an L * P whose rows do not line up with the shuffle groups
+// (five levels x four points = 20).  sm: 2 x rows x LP floats; the exponentials are sm[rows * LP + s].  Ends with a barrier.
+template <typename PT>
+__device__ __forceinline__ void tile_exp_to_lds(const PT *logit, const Tile t, int rows, int M, int LP, int Lq, float *sm)
+{
+    const int total = rows * LP;
+    for (int s = threadIdx.x; s < total; s += 256) {
+        const int r = s / LP;
+        sm[s] = t.q0 + r < Lq ? RawOp<PT>::ld_logit(logit, (((int64_t)t.n * Lq + t.q0 + r) * M + t.m) * LP + (s - r * LP)) : 0.f;
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < total; s += 256) {
+        const float *lr = sm + (s / LP) * LP;
+        float mx = lr[0];
+        for (int j = 1; j < LP; ++j) mx = fmaxf(mx, lr[j]);
+        sm[total + s] = __expf(sm[s] - mx);
+    }
+    __syncthreads();
+}
+
+// One sample record of a tile from the raw operands: the softmax weight `a` of the sample (fp32, over the row's L * P logits),
+// its location by msda_geom.h's fused_loc_xy, its corners by sample_setup_oob, and a corner on a padded pixel -> kOob (never
+// loaded, no gradient).  Called by ALL threads of the workgroup (the softmax reduces across lanes); `in`: the thread has a
+// sample slot, `live`: that slot's query row exists.  Returns whether the sample is on the map.
+template <typename PT>
+__device__ __forceinline__ bool fused_record(const Prologue<PT> &pg, __amdgpu_buffer_rsrc_t rr, const int64_t *__restrict__ shapes,
+                                             const int64_t *__restrict__ starts, const float *sm_e, bool in, bool live, int n, int q,
+                                             int64_t row, int r, int k, int S, int L, int P, unsigned row_bytes, unsigned (&off)[4],
+                                             float &lw, float &lh, float &a)
+{
+    const int LP = L * P, l = k / P;
+    float2 o = make_float2(0.f, 0.f);
+    float4 rp = make_float4(0.f, 0.f, 0.f, 0.f);
+    float raw = 0.f;
+    int H = 1, W = 1, st = 0;
+    const bool shuf = lp_shuffles(LP);      // (workgroup-uniform)
+    if (live) {
+        o = RawOp<PT>::ld_off(pg.off, row * LP + k);
+        if (shuf) raw = RawOp<PT>::ld_logit(pg.logit, row * LP + k);
+        rp = ld_ref(rr, q * L + l, pg.ref_dim);
+        H = (int)shapes[2 * l];
+        W = (int)shapes[2 * l + 1];
+        st = (int)starts[l];
+    }
+    if (shuf) {      // __expf / v_rcp_f32 as the fp32 kernels' row_softmax (msda_fast.h)
+        const float e = __expf(raw - lp_group_max(raw, LP));
+        a = e * fast_rcp(lp_group_sum(e, LP));
+    } else {
+        float sum = 0.f;
+        if (in)
+            for (int j = 0; j < LP; ++j) sum += sm_e[r * LP + j];      // fixed order
+        a = in ? sm_e[r * LP + k] * fast_rcp(sum) : 0.f;
+    }
+    off[0] = off[1] = off[2] = off[3] = kOob;
+    lw = lh = 0.f;
+    if (!live) return false;
+    float x, y;
+    fused_loc_xy(o, rp, pg.ref_dim, P, H, W, x, y);
+    if (!sample_setup_oob(x, y, H, W, st, row_bytes, off, lw, lh)) return false;
+    if (pg.mask) {      // (x, y) -> top-left pixel exactly as sample_setup_oob derives it
+        const int h0 = (int)floorf(sub_rn(mul_rn(y, (float)H), 0.5f)), w0 = (int)floorf(sub_rn(mul_rn(x, (float)W), 0.5f));
+        const int pix = st + h0 * W + w0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int p = pix + (c & 1) + (c >> 1) * W;
+            // (a level table that does not tile [0, S) must not reach past the mask)
+            if (off[c] != kOob && ((unsigned)p >= (unsigned)S || pg.mask[(int64_t)n * S + p] != 0)) off[c] = kOob;
+        }
+    }
+    return true;
+}
+
+// forward: msda_fwd_h16 with phase 1 from the raw operands.  LDS: the records + 2 x RPB x L * P floats when L * P is no power of two.
+template <typename T16, typename PT, int SPLIT>
+__global__ __launch_bounds__(256) void msda_fwd_h16_fused(const T16 *__restrict__ value, const int64_t *__restrict__ shapes,
+                                                          const int64_t *__restrict__ starts, const Prologue<PT> pg, int S, int M,
+                                                          int L, int Lq, int P, int tiles_per_image, T16 *__restrict__ out)
+{
+    constexpr int RPB = 32 / SPLIT;
+    extern __shared__ float4 smem[];
+    const int LP = L * P, LPP = LP + 1, total = RPB * LP;
+    int4 *rec_off = reinterpret_cast<int4 *>(smem);
+    float4 *rec_w = smem + RPB * LPP;
+    float *sm = reinterpret_cast<float *>(smem + 2 * RPB * LPP);
+    const Tile t = tile_of_block(M, tiles_per_image, RPB);
+    const unsigned row_bytes = (unsigned)(M * kD) * 2u;
+    if (!lp_shuffles(LP)) tile_exp_to_lds<PT>(pg.logit, t, RPB, M, LP, Lq, sm);
+    const __amdgpu_buffer_rsrc_t rr = image_rsrc(pg.ref + (int64_t)t.n * Lq * L * pg.ref_dim, (unsigned)(Lq * L * pg.ref_dim) * 4u);
+
+    // ---- phase 1: sample records (every thread walks every trip: the softmax reduces across lanes)
+    for (int s0 = 0; s0 < total; s0 += 256) {
+        const int s = s0 + (int)threadIdx.x;
+        const bool in = s < total;
+        const int r = in ? s / LP : 0, k = in ? s - r * LP : 0;
+        const int q = t.q0 + r;
+        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
+        unsigned off[4];
+        float lw, lh, a;
+        float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (fused_record<PT>(pg, rr, shapes, starts, sm + total, in, in && q < Lq, t.n, q, row, r, k, S, L, P, row_bytes, off, lw, lh, a)) {
+            const float hh = 1.f - lh, hw = 1.f - lw;
+            w = make_float4(a * (hh * hw), a * (hh * lw), a * (lh * hw), a * (lh * lw));
+        }
+        if (in) {
+            rec_off[r * LPP + k] = make_int4((int)off[0], (int)off[1], (int)off[2], (int)off[3]);
+            rec_w[r * LPP + k] = w;
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: gather + weighted sum in fp32
+    fwd_gather_store<T16, SPLIT>(value, rec_off, rec_w, t, S, M, LP, LPP, Lq, out);
+}
+
+// backward: msda_bwd_h16 with the records from the raw operands and the fused epilogue in the write-back: the softmax backward
+// grad_logits = a_k (g_k - sum_j a_j g_j) with the row's dot from LDS in a fixed order, grad_offsets = grad_loc * scale; both
+// rounded once when PT is 16-bit.  LDS: as msda_bwd_h16 + 2 x rpb x L * P floats when L * P is no power of two.
+template <typename T16, typename PT>
+__global__ __launch_bounds__(256) void msda_bwd_h16_fused(const T16 *__restrict__ gout, const T16 *__restrict__ value,
+                                                          const int64_t *__restrict__ shapes, const int64_t *__restrict__ starts,
+                                                          const Prologue<PT> pg, int S, int M, int L, int Lq, int P,
+                                                          int tiles_per_image, int rpb, float *__restrict__ gws, PT *__restrict__ goff,
+                                                          PT *__restrict__ glogit)
+{
+    extern __shared__ float4 smem[];
+    const int LP = L * P, LPP = LP + 1, total = rpb * LP;
+    int4 *rec_off = reinterpret_cast<int4 *>(smem);
+    float4 *rec_p = smem + rpb * LPP;      // {lw, lh, a, level}; overwritten with {g_attn, g_x, g_y, a}
+    float *lev_w = reinterpret_cast<float *>(smem + 2 * rpb * LPP), *lev_h = lev_w + kMaxLevels;
+    float *sm = lev_h + kMaxLevels;
+    const Tile t = tile_of_block(M, tiles_per_image, rpb);
+    const unsigned row_bytes = (unsigned)(M * kD) * 2u;
+    if (threadIdx.x < L) {
+        lev_h[threadIdx.x] = (float)shapes[2 * threadIdx.x];
+        lev_w[threadIdx.x] = (float)shapes[2 * threadIdx.x + 1];
+    }
+    if (!lp_shuffles(LP)) tile_exp_to_lds<PT>(pg.logit, t, rpb, M, LP, Lq, sm);
+    const __amdgpu_buffer_rsrc_t rr = image_rsrc(pg.ref + (int64_t)t.n * Lq * L * pg.ref_dim, (unsigned)(Lq * L * pg.ref_dim) * 4u);
+    for (int s0 = 0; s0 < total; s0 += 256) {
+        const int s = s0 + (int)threadIdx.x;
+        const bool in = s < total;
+        const int r = in ? s / LP : 0, k = in ? s - r * LP : 0;
+        const int q = t.q0 + r;
+        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
+        unsigned off[4];
+        float lw, lh, a;
+        fused_record<PT>(pg, rr, shapes, starts, sm + total, in, in && q < Lq, t.n, q, row, r, k, S, L, P, row_bytes, off, lw, lh, a);
+        if (in) {      // `a` is kept for skipped samples too: the softmax backward needs every probability
+            rec_off[r * LPP + k] = make_int4((int)off[0], (int)off[1], (int)off[2], (int)off[3]);
+            rec_p[r * LPP + k] = make_float4(lw, lh, q < Lq ? a : 0.f, __int_as_float(k / P));
+        }
+    }
+    __syncthreads();
+
+    bwd_rows<T16>(gout, value, rec_off, rec_p, lev_w, lev_h, t, S, M, LP, LPP, Lq, rpb, gws);
+    __syncthreads();
+
+    // ---- coalesced write-back of grad_attn_logits / grad_sampling_offsets, each in PT
+    for (int s = threadIdx.x; s < total; s += 256) {
+        const int r = s / LP, k = s - r * LP;
+        const int q = t.q0 + r;
+        if (q >= Lq) continue;
+        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
+        const float4 *rowp = rec_p + r * LPP;
+        const float4 res = rowp[k];      // {d/d a_k, d/d loc.x, d/d loc.y, a_k}
+        float dot = 0.f;
+        for (int j = 0; j < LP; ++j) dot += rowp[j].w * rowp[j].x;
+        const int l = k / P;
+        const float2 sc = fused_loc_scale(ld_ref(rr, q * L + l, pg.ref_dim), pg.ref_dim, P, (int)lev_h[l], (int)lev_w[l]);
+        RawOp<PT>::st_logit(glogit, row * LP + k, res.w * (res.x - dot));
+        RawOp<PT>::st_off(goff, row * LP + k, make_float2(res.y * sc.x, res.z * sc.y));
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -476,7 +741,149 @@ int backward_impl(hipStream_t st, const T16 *gout, const T16 *value, const int64
     return semidetr::launch_status("msda_h16_convert");
 }
 
+// ---- fused prologue / epilogue: the fast kernels or SEMIDETR_E_BADARG (there is no generic fused kernel)
+struct FusedArgs {
+    const void *value;
+    const int64_t *shapes, *starts;
+    const float *ref;
+    int ref_dim;
+    const void *off, *logit;
+    int prologue_type;
+    const unsigned char *mask;
+    int N, S, M, D, L, Lq, P;
+};
+
+// LDS of a fused kernel with `rows` query rows: the records (+ the backward's level table) + the softmax rows when L * P is no power of two
+size_t fused_lds(int rows, int LP, bool backward)
+{
+    const bool shuf = (LP & (LP - 1)) == 0;
+    return (size_t)rows * (LP + 1) * 32 + (backward ? 2 * kMaxLevels * sizeof(float) : 0) + (shuf ? 0 : (size_t)2 * rows * LP * sizeof(float));
+}
+
+int check_fused(const FusedArgs &a, int dtype, const void *io16, const char *what)
+{
+    if (int rc = check_common(a.value, a.shapes, a.starts, a.off, a.logit, dtype, a.N, a.S, a.M, a.D, a.L, a.Lq, a.P)) return rc;
+    SEMIDETR_REQUIRE(a.ref && io16, SEMIDETR_E_BADARG, "%s: null pointer argument", what);
+    SEMIDETR_REQUIRE(a.ref_dim == 2 || a.ref_dim == 4, SEMIDETR_E_BADARG, "%s: ref_dim must be 2 or 4, got %d", what, a.ref_dim);
+    SEMIDETR_REQUIRE(a.prologue_type == SEMIDETR_ROW_F32 || a.prologue_type == (dtype == SEMIDETR_H16_FP16 ? SEMIDETR_ROW_FP16 : SEMIDETR_ROW_BF16),
+                     SEMIDETR_E_BADARG, "%s: prologue_type must be SEMIDETR_ROW_F32 (0) or the 16-bit type of dtype (%s), got %d", what,
+                     dtype == SEMIDETR_H16_FP16 ? "SEMIDETR_ROW_FP16 (1)" : "SEMIDETR_ROW_BF16 (2)", a.prologue_type);
+    SEMIDETR_REQUIRE(a.D == kD && a.M <= 32, SEMIDETR_E_BADARG,
+                     "%s: the fused 16-bit kernels take channels == 32 and num_heads <= 32 (got %d, %d); there is no generic fused kernel",
+                     what, a.D, a.M);
+    SEMIDETR_REQUIRE(a.L <= kMaxLevels && (int64_t)a.L * a.P <= 64, SEMIDETR_E_BADARG,
+                     "%s: num_levels * num_point = %lld exceeds the 64 samples per row the fused 16-bit kernels hold in LDS", what,
+                     (long long)a.L * a.P);
+    SEMIDETR_REQUIRE((((uintptr_t)a.value | (uintptr_t)io16 | (uintptr_t)a.ref | (uintptr_t)a.off) & 7) == 0 && ((uintptr_t)a.logit & 3) == 0,
+                     SEMIDETR_E_BADARG,
+                     "%s: value, out / grad_out, reference_points and sampling_offsets must be 8-byte aligned, attn_logits 4-byte aligned",
+                     what);
+    SEMIDETR_REQUIRE((int64_t)a.S * a.M * kD * 2 < (int64_t)kOob && (int64_t)a.Lq * a.L * a.ref_dim * 4 < (int64_t)kOob, SEMIDETR_E_TOOLARGE,
+                     "%s: an image's value slice or reference points exceed the buffer instructions' 32-bit byte range", what);
+    return SEMIDETR_OK;
+}
+
+template <typename T16, typename PT>
+int fused_forward_impl(hipStream_t st, const FusedArgs &a, T16 *out)
+{
+    const Prologue<PT> pg = {a.ref, static_cast<const PT *>(a.off), static_cast<const PT *>(a.logit), a.mask, a.ref_dim};
+    const T16 *value = static_cast<const T16 *>(a.value);
+    const int LP = a.L * a.P;
+    int split = pick_split(a.N, a.Lq, a.M);
+    while (split < 4 && fused_lds(32 / split, LP, false) > 64 * 1024) split *= 2;
+    const int rpb = 32 / split;
+    const int tiles = (a.Lq + rpb - 1) / rpb;
+    SEMIDETR_REQUIRE((int64_t)a.N * tiles * a.M < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_fused_forward_h16: grid too large");
+    const size_t lds = fused_lds(rpb, LP, false);
+    const dim3 grid((unsigned)((int64_t)a.N * tiles * a.M));
+    if (split == 1)
+        hipLaunchKernelGGL((msda_fwd_h16_fused<T16, PT, 1>), grid, dim3(256), lds, st, value, a.shapes, a.starts, pg, a.S, a.M, a.L, a.Lq, a.P, tiles, out);
+    else if (split == 2)
+        hipLaunchKernelGGL((msda_fwd_h16_fused<T16, PT, 2>), grid, dim3(256), lds, st, value, a.shapes, a.starts, pg, a.S, a.M, a.L, a.Lq, a.P, tiles, out);
+    else
+        hipLaunchKernelGGL((msda_fwd_h16_fused<T16, PT, 4>), grid, dim3(256), lds, st, value, a.shapes, a.starts, pg, a.S, a.M, a.L, a.Lq, a.P, tiles, out);
+    g_last_kernels = split == 1 ? "msda_fwd_h16_fused<1" : (split == 2 ? "msda_fwd_h16_fused<2" : "msda_fwd_h16_fused<4");
+    return semidetr::launch_status("msda_fwd_h16_fused");
+}
+
+template <typename T16, typename PT>
+int fused_backward_impl(hipStream_t st, const FusedArgs &a, const T16 *gout, float *ws, T16 *gvalue, void *goff, void *glogit)
+{
+    const Prologue<PT> pg = {a.ref, static_cast<const PT *>(a.off), static_cast<const PT *>(a.logit), a.mask, a.ref_dim};
+    const int LP = a.L * a.P;
+    // 32 query rows per workgroup, 8 when that would not fill the chip or 32 rows would not fit 64 KB of LDS (as backward_impl)
+    const int rpb = ((int64_t)a.N * a.M * ((a.Lq + 31) / 32) >= 1024 && fused_lds(32, LP, true) <= 64 * 1024) ? 32 : 8;
+    const int tiles = (a.Lq + rpb - 1) / rpb;
+    SEMIDETR_REQUIRE((int64_t)a.N * tiles * a.M < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_fused_backward_h16: grid too large");
+    hipLaunchKernelGGL((msda_bwd_h16_fused<T16, PT>), dim3((unsigned)((int64_t)a.N * tiles * a.M)), dim3(256), fused_lds(rpb, LP, true), st, gout,
+                       static_cast<const T16 *>(a.value), a.shapes, a.starts, pg, a.S, a.M, a.L, a.Lq, a.P, tiles, rpb, ws,
+                       static_cast<PT *>(goff), static_cast<PT *>(glogit));
+    if (int rc = semidetr::launch_status("msda_bwd_h16_fused")) return rc;
+    const int64_t count = (int64_t)a.N * a.S * a.M * a.D;
+    const int64_t blocks = (count + 2047) / 2048;
+    SEMIDETR_REQUIRE(blocks < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_fused_backward_h16: grad_value too large");
+    if ((((uintptr_t)ws | (uintptr_t)gvalue) & 15) == 0)
+        hipLaunchKernelGGL((msda_h16_convert<T16, true>), dim3((unsigned)blocks), dim3(256), 0, st, ws, count, gvalue);
+    else
+        hipLaunchKernelGGL((msda_h16_convert<T16, false>), dim3((unsigned)blocks), dim3(256), 0, st, ws, count, gvalue);
+    g_last_kernels = "msda_bwd_h16_fused+msda_h16_convert";
+    return semidetr::launch_status("msda_h16_convert");
+}
+
 }  // namespace semidetr_h16
+
+extern "C" int semidetr_msda_fused_forward_h16(void *stream, int dtype, const void *value, const int64_t *spatial_shapes,
+                                               const int64_t *level_start, const float *reference_points, int ref_dim,
+                                               const void *sampling_offsets, const void *attn_logits, int prologue_type,
+                                               const unsigned char *padding_mask, int batch, int spatial_size, int num_heads,
+                                               int channels, int num_levels, int num_query, int num_point, void *out)
+{
+    using namespace semidetr_h16;
+    const FusedArgs a = {value, spatial_shapes, level_start, reference_points, ref_dim, sampling_offsets, attn_logits, prologue_type,
+                         padding_mask, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point};
+    if (int rc = check_fused(a, dtype, out, "msda_fused_forward_h16")) return rc;
+    const hipStream_t st = semidetr::as_stream(stream);
+    const bool f32 = prologue_type == SEMIDETR_ROW_F32;
+    if (dtype == SEMIDETR_H16_FP16)
+        return f32 ? fused_forward_impl<__half, float>(st, a, static_cast<__half *>(out))
+                   : fused_forward_impl<__half, __half>(st, a, static_cast<__half *>(out));
+    return f32 ? fused_forward_impl<__hip_bfloat16, float>(st, a, static_cast<__hip_bfloat16 *>(out))
+               : fused_forward_impl<__hip_bfloat16, __hip_bfloat16>(st, a, static_cast<__hip_bfloat16 *>(out));
+}
+
+extern "C" int semidetr_msda_fused_backward_h16(void *stream, int dtype, const void *grad_out, const void *value,
+                                                const int64_t *spatial_shapes, const int64_t *level_start,
+                                                const float *reference_points, int ref_dim, const void *sampling_offsets,
+                                                const void *attn_logits, int prologue_type, const unsigned char *padding_mask,
+                                                int batch, int spatial_size, int num_heads, int channels, int num_levels,
+                                                int num_query, int num_point, void *workspace, void *grad_value,
+                                                void *grad_sampling_offsets, void *grad_attn_logits)
+{
+    using namespace semidetr_h16;
+    const FusedArgs a = {value, spatial_shapes, level_start, reference_points, ref_dim, sampling_offsets, attn_logits, prologue_type,
+                         padding_mask, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point};
+    if (int rc = check_fused(a, dtype, grad_out, "msda_fused_backward_h16")) return rc;
+    SEMIDETR_REQUIRE(workspace && grad_value && grad_sampling_offsets && grad_attn_logits, SEMIDETR_E_BADARG,
+                     "msda_fused_backward_h16: null pointer argument");
+    SEMIDETR_REQUIRE(((uintptr_t)grad_value & 1) == 0 && ((uintptr_t)workspace & 3) == 0 && ((uintptr_t)grad_sampling_offsets & 7) == 0 &&
+                         ((uintptr_t)grad_attn_logits & 3) == 0,
+                     SEMIDETR_E_BADARG,
+                     "msda_fused_backward_h16: grad_value must be 2-byte, workspace and grad_attn_logits 4-byte, grad_sampling_offsets "
+                     "8-byte aligned");
+    const hipStream_t st = semidetr::as_stream(stream);
+    float *ws = static_cast<float *>(workspace);
+    const bool f32 = prologue_type == SEMIDETR_ROW_F32;
+    if (dtype == SEMIDETR_H16_FP16) {
+        const __half *go = static_cast<const __half *>(grad_out);
+        __half *gv = static_cast<__half *>(grad_value);
+        return f32 ? fused_backward_impl<__half, float>(st, a, go, ws, gv, grad_sampling_offsets, grad_attn_logits)
+                   : fused_backward_impl<__half, __half>(st, a, go, ws, gv, grad_sampling_offsets, grad_attn_logits);
+    }
+    const __hip_bfloat16 *go = static_cast<const __hip_bfloat16 *>(grad_out);
+    __hip_bfloat16 *gv = static_cast<__hip_bfloat16 *>(grad_value);
+    return f32 ? fused_backward_impl<__hip_bfloat16, float>(st, a, go, ws, gv, grad_sampling_offsets, grad_attn_logits)
+               : fused_backward_impl<__hip_bfloat16, __hip_bfloat16>(st, a, go, ws, gv, grad_sampling_offsets, grad_attn_logits);
+}
 
 extern "C" const char *semidetr_msda_h16_last_kernels(void) { return semidetr_h16::g_last_kernels; }
 

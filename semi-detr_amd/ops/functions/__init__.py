@@ -1,1 +1,1 @@
-from .ms_deform_attn_func import MSDeformAttnFunction, MSDeformAttnFusedFunction, MSDeformAttnMixedFunction  # noqa: F401
+from .ms_deform_attn_func import MSDeformAttnFunction, MSDeformAttnFusedFunction, MSDeformAttnMixedFunction, MSDeformAttnMixedFusedFunction  # noqa: F401

@@ -65,6 +65,33 @@ class MSDeformAttnMixedFunction(Function):
         return grad_value, None, None, grad_sampling_loc, grad_attn_weight, None
 
 
+class MSDeformAttnMixedFusedFunction(Function):
+    """``MSDeformAttnFusedFunction`` on a 16-bit value map: ``apply(value16, spatial_shapes, level_start_index, reference_points,
+    sampling_offsets, attn_logits[, padding_mask])``.  ``value16`` is fp16 or bf16 and so are the output and ``grad_value``;
+    offsets and logits are the Linear layers' RAW outputs, both of value's dtype or both fp32, and their gradients come back in
+    that dtype; reference points are fp32 (16-bit points are up-cast exactly by the front end).  Softmax, location arithmetic, the
+    padding mask and their backward run in fp32 inside the 16-bit kernels and every 16-bit result is rounded once
+    (include/semidetr_hip.h: semidetr_msda_fused_forward_h16).  The 16-bit value and the raw operands are what is saved for the
+    backward.  No gradient flows to ``reference_points``: the caller routes a call whose points require one elsewhere."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, reference_points, sampling_offsets, attn_logits, padding_mask=None):
+        if padding_mask is not None:
+            padding_mask = padding_mask.contiguous()
+        output = MSDA.ms_deform_attn_h16_fused_forward(value, spatial_shapes, level_start_index, reference_points, sampling_offsets,
+                                                       attn_logits, padding_mask)
+        ctx.save_for_backward(value, spatial_shapes, level_start_index, reference_points, sampling_offsets, attn_logits, padding_mask)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        value, shapes, starts, ref, off, logits, padding_mask = ctx.saved_tensors
+        grad_value, grad_off, grad_logits = MSDA.ms_deform_attn_h16_fused_backward(
+            value, shapes, starts, ref, off, logits, grad_output.contiguous(), padding_mask)
+        return (grad_value, None, None, None, grad_off, grad_logits, None)[:len(ctx.needs_input_grad)]
+
+
 class MSDeformAttnFusedFunction(Function):
     """MSDeformAttn.forward between the Linear layers as ONE op: consumes the
     reference points, the raw sampling offsets and the raw attention logits; softmax, location arithmetic

@@ -16,7 +16,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from ... import MultiScaleDeformableAttention as MSDA
-from ..functions import MSDeformAttnFunction, MSDeformAttnFusedFunction, MSDeformAttnMixedFunction
+from ..functions import (MSDeformAttnFunction, MSDeformAttnFusedFunction, MSDeformAttnMixedFunction,
+                         MSDeformAttnMixedFusedFunction)
 
 
 def _is_power_of_2(n):
@@ -69,6 +70,11 @@ class MSDeformAttn(nn.Module):
         # is: 16-bit value / output / grad_value, fp32 locations and weights, fp32 arithmetic.  False restores the
         # up-cast route (value.float() -> the fp32 op -> .to(dtype)).  Plain attribute like fuse_prologue, not in state_dict.
         self.native_16bit = True
+        # Opt-in: a 16-bit call that would take the mixed-precision kernels hands them the Linear layers' RAW 16-bit offsets and
+        # logits, the reference points and the padding mask instead -- softmax, location arithmetic and mask inside the kernels, in
+        # fp32, none of the fp32 (N,Lq,M,L,P[,2]) intermediates in HBM.  Off by default: the results differ from
+        # torch's autocast sequence, which forms offsets / normalizer in 16 bits (here that product is fp32).  Plain attribute.
+        self.fuse_prologue_16bit = False
         # Which of the two encoder forward kernels runs follows how far THIS instance's learned offsets reach (semidetr_hip.h:
         # SEMIDETR_MSDA_POLICY_SLOT): instances take consecutive slots 1..255 (the reference builds 12 per model,
         # transformer.py:609,760; beyond 255 instances slots are shared, which only mixes their counts).  Plain attribute.
@@ -89,6 +95,7 @@ class MSDeformAttn(nn.Module):
         self.__dict__["policy_slot"] = _next_policy_slot()
         self.__dict__.setdefault("fuse_prologue", True)
         self.__dict__.setdefault("native_16bit", True)
+        self.__dict__.setdefault("fuse_prologue_16bit", False)
 
     def _reset_parameters(self):
         # ms_deform_attn.py:62-76 -- head m looks along direction 2*pi*m/M, point i at distance i+1
@@ -106,6 +113,20 @@ class MSDeformAttn(nn.Module):
         nn.init.constant_(self.value_proj.bias.data, 0.0)
         nn.init.xavier_uniform_(self.output_proj.weight.data)
         nn.init.constant_(self.output_proj.bias.data, 0.0)
+
+    def _takes_fused_16bit_route(self, value, reference_points, offsets, logits, shapes, starts):
+        """fuse_prologue_16bit, on exactly the calls the mixed-precision kernels take today (native_16bit and the routing rule
+        above) whose operands the fused 16-bit kernels accept and whose reference points need no gradient (the op returns none)."""
+        if not (getattr(self, "fuse_prologue_16bit", False) and getattr(self, "native_16bit", True)):
+            return False
+        if value.dtype not in (torch.float16, torch.bfloat16) or not MSDA.fused_h16_supported(value, reference_points, offsets, logits):
+            return False
+        if torch.is_grad_enabled() and reference_points.requires_grad:
+            return False
+        N, Len_in, Len_q = value.shape[0], value.shape[1], offsets.shape[1]
+        follows = torch.is_grad_enabled() and (value.requires_grad or offsets.requires_grad or logits.requires_grad)
+        pixels = Len_q == Len_in and bool(MSDA.pyramid_check(shapes, starts, Len_in) & 2)
+        return not _h16_takes_upcast_route(pixels, N * Len_q, follows)
 
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
                 input_padding_mask=None):
@@ -134,6 +155,11 @@ class MSDeformAttn(nn.Module):
                                                      input_level_start_index, reference_points.contiguous(),
                                                      offsets.contiguous(), logits.contiguous(), input_padding_mask,
                                                      getattr(self, "policy_slot", 0))
+            return self.output_proj(output)
+        if self._takes_fused_16bit_route(value, reference_points, offsets, logits, input_spatial_shapes, input_level_start_index):
+            output = MSDeformAttnMixedFusedFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index,
+                                                          reference_points.contiguous(), offsets.contiguous(), logits.contiguous(),
+                                                          input_padding_mask)
             return self.output_proj(output)
         if input_padding_mask is not None:
             value = value.masked_fill(input_padding_mask[..., None, None], float(0))
