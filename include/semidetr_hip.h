@@ -1021,6 +1021,82 @@ int semidetr_add_norm_forward_mixed(void *stream, const semidetr_add_norm_mixed 
 int semidetr_add_norm_backward_mixed(void *stream, const semidetr_add_norm_mixed *params /* host */, void *workspace,
                                      size_t workspace_bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * Input projection: GroupNorm(32, 256) of every pyramid level written straight into the token tensor (ABI 7, additive)
+ * (csrc/group_norm_tokens.hip).
+ * Replaces, per level l, the GroupNorm of  nn.Sequential(Conv2d, GroupNorm(32, 256))  (dino_detr_ssod_head.py:251-259,
+ * dino_detr_head.py:223-231) and, in the transformer,  src.flatten(2).transpose(1, 2),  torch.cat(src_flatten, 1)  and the
+ * src + pos  in front of encoder layer 0 (detr_od/models/utils/transformer.py:1276-1287, 635).
+ *
+ *   per (image n, level l, group g of 8 channels):  mean = mean(x),  var = mean((x - mean)^2)  (biased) over the 8 * hw[l]
+ *   elements of the group;  rstd = 1 / sqrt(var + eps);
+ *   tokens[n, start[l] + p, c] = (x_l[n, c, p] - mean) * rstd * weight_l[c] + bias_l[c];   q = tokens + pos.
+ * A call writes the rows [start[l], start[l] + hw[l]) of its levels and no other row of tokens and q: the levels of a pyramid may
+ * be written by more than one call into the same tensors (a level whose input is computed from an earlier level's rows).
+ *
+ * x[l] is (batch, 256, hw[l]): element (n, c, p) at x[l] + n * x_batch_stride[l] + c * hw[l] + p (every image a contiguous
+ * NCHW block; the batch stride, in ELEMENTS, is free), of type x_type (SEMIDETR_ROW_*).  tokens and q are contiguous
+ * (batch, S, 256) of type out_type: fp32, or x_type where that is a 16-bit type.  pos (type pos_type, any of the three), gy and gq
+ * (type out_type) are (batch, S, 256) read through the strides of their two leading dimensions in ELEMENTS, last stride 1.
+ * grad_x[l] is contiguous (batch, 256, hw[l]) of type x_type.  weight[l], bias[l], grad_weight[l], grad_bias[l] are fp32 vectors
+ * of 256; mean and rstd are fp32 (batch, levels, 32).  Alignment: x[l], grad_x[l] and every token row 16-byte (fp32) or 8-byte
+ * (16-bit), batch strides and token strides multiples of 4 elements, the parameter vectors and the workspace 16-byte.  A plane
+ * (n, c) starts wherever c * hw[l] puts it: the kernels read and write planes 16 (8) bytes per lane where hw[l] % 4 == 0 and one
+ * element per lane otherwise.
+ * Arithmetic in fp32 on exactly up-cast operands; a 16-bit result is rounded once, to nearest even, from the unrounded fp32
+ * value (q from the unrounded tokens + pos).  No float atomics, no memset, bitwise reproducible: every grid, map and order of a
+ * sum depends on batch, levels and hw[] alone.
+ *
+ * semidetr_gn_tokens_forward  -- two launches for the whole pyramid.
+ *   1. statistics: one workgroup per chunk of 8192 consecutive elements of a group (a group of level l has
+ *      ceil(8 * hw[l] / 8192) chunks).  Reads x; writes per chunk its sum and the sum of squared deviations from ITS OWN mean
+ *      into the workspace.
+ *   2. normalise + transpose: one workgroup per (image, level, tile of 64 pixels).  Reads the chunks of its 32 groups and merges
+ *      them in a fixed order in fp64 (mean = sum of sums / count; M2 = sum of (M2_c + count_c * (mean_c - mean)^2); one rounding
+ *      each), reads x, weight[l], bias[l] and pos (NULL exactly where q is NULL); writes complete 256-channel rows of tokens
+ *      and q through a transposing LDS tile, and mean and rstd (the workgroup of a level's first tile).
+ * semidetr_gn_tokens_backward -- three launches, two where every grad_weight[l] and grad_bias[l] is NULL.  gy and gq are the
+ *   upstream gradients of tokens and q; either may be NULL, not both; gq itself is the gradient of pos.  With g = gy + gq and
+ *   xhat = (x - mean) * rstd recomputed:
+ *   1. sums: one workgroup per (image, level, unit of 128 pixels).  Reads x, gy, gq, mean, rstd, weight[l]; writes one slot of
+ *      the workspace: per channel sum g * xhat and sum g over its pixels, per group sum g * w and sum g * w * xhat.
+ *   2. dx: one workgroup per (image, level, tile of 64 pixels).  Merges the group sums of its level's units in a fixed order in
+ *      fp64 (one rounding), reads gy, gq token-major and x, writes
+ *      grad_x = rstd * (g * w - mean_group(g * w) - xhat * mean_group(g * w * xhat))  as NCHW through the same tile.
+ *   3. parameter reduce: per level, the slots in 16 contiguous parts in index order in fp64, the parts in order, one rounding:
+ *      grad_weight[l] = sum g * xhat, grad_bias[l] = sum g  (each may be NULL; a level with both NULL is skipped).
+ *   bias, tokens, q and pos are not read.  grad_x[l] is written for every level.
+ * workspace: semidetr_gn_tokens_workspace_bytes(params, for_backward) bytes, 16-byte aligned, no initialisation needed; 0 for
+ *   a block outside the limits.  The forward and the backward may share one buffer.
+ * Checked on the host before any launch (SEMIDETR_E_BADARG, nothing is written): channels != 256, groups != 32, levels outside
+ *   1 .. SEMIDETR_GN_MAX_LEVELS, batch < 1, hw[l] < 1, levels whose rows overlap, are out of order or pass tokens_per_image, a
+ *   NULL operand, q without pos or pos without q, neither gy nor gq, an unknown type code, an out_type that is neither fp32 nor
+ *   x_type, a misaligned pointer or stride, a workspace that is too small.
+ *   SEMIDETR_E_TOOLARGE: batch * tokens_per_image * 256 >= 2^31, batch > 65535 or a batch stride >= 2^31.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_GN_MAX_LEVELS 8
+typedef struct semidetr_gn_tokens {
+    int batch, levels, channels, groups;                  /* channels == 256, groups == 32 */
+    float eps;
+    int64_t hw[SEMIDETR_GN_MAX_LEVELS], start[SEMIDETR_GN_MAX_LEVELS];   /* pixels of level l; its first token row */
+    int64_t tokens_per_image;                             /* S: rows of tokens per image, >= start[l] + hw[l] */
+    const void *x[SEMIDETR_GN_MAX_LEVELS];                /* (batch, 256, hw[l]) */
+    int64_t x_batch_stride[SEMIDETR_GN_MAX_LEVELS];       /* in elements */
+    const float *weight[SEMIDETR_GN_MAX_LEVELS], *bias[SEMIDETR_GN_MAX_LEVELS];
+    void *grad_x[SEMIDETR_GN_MAX_LEVELS];                 /* backward: written */
+    float *grad_weight[SEMIDETR_GN_MAX_LEVELS], *grad_bias[SEMIDETR_GN_MAX_LEVELS];   /* backward: written; NULL = not wanted */
+    void *tokens, *q;                                     /* forward: written; q NULL = no pos */
+    const void *pos, *gy, *gq;                            /* pos: forward; gy, gq: backward */
+    int64_t pos_stride[2], gy_stride[2], gq_stride[2];    /* in elements */
+    float *mean, *rstd;                                   /* (batch, levels, 32); forward: written; backward: read */
+    int x_type, out_type, pos_type;                       /* SEMIDETR_ROW_* */
+} semidetr_gn_tokens;
+size_t semidetr_gn_tokens_workspace_bytes(const semidetr_gn_tokens *params /* host */, int for_backward);
+int semidetr_gn_tokens_forward(void *stream, const semidetr_gn_tokens *params /* host */, void *workspace,
+                               size_t workspace_bytes);
+int semidetr_gn_tokens_backward(void *stream, const semidetr_gn_tokens *params /* host */, void *workspace,
+                                size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,8 @@ from .self_attn import (MaskedAttentionFunction, MaskedAttentionH16Function, Mul
 from .add_norm import (AddLayerNormFunction, LayerNorm, add_layer_norm, convert_layer_norms, decoder_layer_forward,  # noqa: E402,F401
                        decoder_layer_forward_ca, decoder_layer_forward_ffn, decoder_layer_forward_sa, encoder_forward,
                        encoder_layer_forward)
+from .input_proj import (GroupNormTokensFunction, group_norm_to_tokens, group_norm_tokens_backward,  # noqa: E402,F401
+                         group_norm_tokens_forward, project_pyramid)
 from .pseudo_label import (filter_pseudo_labels, get_bboxes_for_pseudo_label, teacher_pseudo_labels,  # noqa: E402,F401
                            transform_bboxes)
 
@@ -47,4 +49,6 @@ __all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttnMix
            "get_bboxes", "detection_results", "PendingDetections", "consistency_loss", "ConsistencyLossFunction",
            "masked_attention", "MaskedAttentionFunction", "MaskedAttentionH16Function", "MultiheadAttention", "convert_self_attention",
            "add_layer_norm", "AddLayerNormFunction", "LayerNorm", "convert_layer_norms", "encoder_layer_forward", "encoder_forward",
-           "decoder_layer_forward", "decoder_layer_forward_sa", "decoder_layer_forward_ca", "decoder_layer_forward_ffn"]
+           "decoder_layer_forward", "decoder_layer_forward_sa", "decoder_layer_forward_ca", "decoder_layer_forward_ffn",
+           "group_norm_tokens_forward", "group_norm_tokens_backward", "GroupNormTokensFunction", "group_norm_to_tokens",
+           "project_pyramid"]

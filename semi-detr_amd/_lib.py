@@ -115,12 +115,25 @@ class AddNormMixed(ctypes.Structure):
                             "grad_pos_type"))
 
 
+# the level table of semidetr_gn_tokens: SEMIDETR_GN_MAX_LEVELS entries per field (tests/test_input_proj_ref.py reads the macro
+# back from the header)
+GN_MAX_LEVELS = 8
+_GN_I64, _GN_PTR = c_int64 * GN_MAX_LEVELS, c_void_p * GN_MAX_LEVELS
+
+
+class GnTokens(ctypes.Structure):
+    _fields_ = (_f(c_int, "batch levels channels groups") + _f(c_float, "eps") + _f(_GN_I64, "hw start")
+                + _f(c_int64, "tokens_per_image") + _f(_GN_PTR, "x") + _f(_GN_I64, "x_batch_stride")
+                + _f(_GN_PTR, "weight bias grad_x grad_weight grad_bias") + _f(c_void_p, "tokens q pos gy gq")
+                + _f(_STRIDE2, "pos_stride gy_stride gq_stride") + _f(c_void_p, "mean rstd") + _f(c_int, "x_type out_type pos_type"))
+
+
 # C struct -> mirror, in the header's order
 STRUCTS = {"semidetr_cost_params": CostParams, "semidetr_set_loss_segment": SetLossSegment, "semidetr_dn_layout": DnLayout,
            "semidetr_dn_build": DnBuild, "semidetr_dn_consistency": DnConsistency, "semidetr_consis_layer": ConsisLayer,
            "semidetr_consis_loss": ConsisLoss, "semidetr_self_attn": SelfAttn, "semidetr_self_attn_h16": SelfAttnH16,
            "semidetr_add_norm": AddNorm,
-           "semidetr_add_norm_mixed": AddNormMixed}
+           "semidetr_add_norm_mixed": AddNormMixed, "semidetr_gn_tokens": GnTokens}
 _SEGS, _WORK = POINTER(SetLossSegment), [c_void_p, c_size_t]        # a segment table; the (workspace, workspace_bytes) pair
 
 _MSDA_FWD = [c_void_p] * 6 + [c_int] * 7 + [c_void_p]
@@ -213,6 +226,10 @@ SIGNATURES = {
     "semidetr_add_norm_backward_f32": (c_int, [c_void_p, POINTER(AddNorm)] + _WORK),
     "semidetr_add_norm_forward_mixed": (c_int, [c_void_p, POINTER(AddNormMixed)] + _WORK),
     "semidetr_add_norm_backward_mixed": (c_int, [c_void_p, POINTER(AddNormMixed)] + _WORK),
+    # GroupNorm of the input projection written into the token pyramid (input_proj.py)
+    "semidetr_gn_tokens_workspace_bytes": (c_size_t, [POINTER(GnTokens), c_int]),
+    "semidetr_gn_tokens_forward": (c_int, [c_void_p, POINTER(GnTokens)] + _WORK),
+    "semidetr_gn_tokens_backward": (c_int, [c_void_p, POINTER(GnTokens)] + _WORK),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so
