@@ -1097,6 +1097,75 @@ int semidetr_gn_tokens_forward(void *stream, const semidetr_gn_tokens *params /*
 int semidetr_gn_tokens_backward(void *stream, const semidetr_gn_tokens *params /* host */, void *workspace,
                                 size_t workspace_bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * Reference-point chain of the decoder (csrc/ref_points.hip): everything DINOTransformerDecoder.forward does to the reference
+ * points between two layers (detr_od/models/utils/transformer.py:972-987, 1029-1036) and the head's coordinate loop
+ * (dino_detr_ssod_head.py:393-398), one launch forward and one backward.  A ROW is one (i, j) pair of a segment's two leading
+ * dimensions, i < rows0, j < rows1; `width` in {2, 4} coordinates per row.  The parts of a launch:
+ *
+ *   refine   mode SEMIDETR_REF_REFINE:   new_ref = sigmoid(delta + inverse_sigmoid(ref, eps))
+ *            mode SEMIDETR_REF_SIGMOID:  new_ref = sigmoid(ref)            (ref holds the unsigmoided points; delta is not read)
+ *            mode SEMIDETR_REF_NONE:     new_ref = ref                     (delta is not read; new_ref may be NULL)
+ *            inverse_sigmoid (transformer.py:435-451): x = clamp(x, 0, 1); x1 = max(x, eps); x2 = max(1 - x, eps);
+ *            log(x1 / x2).  sigmoid(t) = 1 / (1 + expf(-t)).  A NaN operand gives NaN.
+ *   scale    valid_ratios != NULL (then num_segments == 1, rows0 = queries, rows1 = images, 1 <= levels <= 8):
+ *            ref_input[j, i, l, c] = new_ref[i, j, c] * valid_ratios[j, l, c & 1]   -- contiguous (rows1, rows0, levels, width)
+ *   embed    embed != NULL (needs the scale part): gen_sineembed_for_position (transformer.py:467-493) of ref_input[:, :, 0, :]:
+ *            embed[i, j, k * 128 + t] = (t even ? sinf : cosf)(fl(fl(coord_k * fp32(2 pi)) / dim_t[t])), the blocks k in the order
+ *            (y, x, w, h) = coordinates (1, 0, 2, 3), or (y, x) for width 2; contiguous (rows0, rows1, 128 * width) fp32.  dim_t is
+ *            the caller's table of 128 fp32 divisors (the kernel evaluates no pow).
+ *
+ * delta and ref are elements of delta_type / ref_type (SEMIDETR_ROW_*), read in place through the strides of their two leading
+ * dimensions, in ELEMENTS, last stride 1.  Arithmetic is fp32 on exactly up-cast operands, every operation rounded on its own;
+ * new_ref has out_type and is rounded once; scale and embed start from the ROUNDED new_ref.  out_type is fp32, or the common
+ * 16-bit type of the operands the mode reads.  valid_ratios, ref_input, embed, dim_t and their gradients are fp32.
+ *
+ * semidetr_ref_points_forward   one launch: a wave takes 8 consecutive rows of a segment, one lane per (row, coordinate) for
+ *   refine and scale, then all 64 lanes write each row of the embed 16 bytes per lane with the lane's dim_t entries in registers.
+ * semidetr_ref_points_backward  one launch, the same map.  With y = new_ref as the forward stored it (read back) and G the
+ *   gradient arriving at new_ref:
+ *     G = g_new + sum_l g_ref_input[j, i, l, c] * vr[j, l, c & 1] + ((sum_t term_t) * fp32(2 pi)) * vr[j, 0, c & 1],
+ *     term_t = (g_embed[.., t] * (t even ? cosf : -sinf)(arg_t)) / dim_t[t], added four per lane in index order, then over 32 lanes
+ *     by a xor butterfly (16, 8, 4, 2, 1): a fixed order.  g_new, g_ref_input, g_embed may each be NULL (a zero).
+ *     REFINE: g_delta = (G * (1 - y)) * y;  g_ref = g_delta * ([x >= eps] / x1 + [1 - x >= eps] / x2), 0 where x is outside
+ *     [0, 1] (torch's clamp rule: the gradient passes at equality).  SIGMOID: g_ref = (G * (1 - y)) * y.  NONE: g_ref = G.
+ *   g_new has out_type and strides; g_delta / g_ref are contiguous (rows0, rows1, width) of delta_type / ref_type, each may be
+ *   NULL (not wanted).  No gradient goes to valid_ratios.  No float atomics, no memset, no workspace: two runs are bitwise equal.
+ * Checked on the host before any launch (SEMIDETR_E_BADARG, nothing is written): width not 2 or 4, an unknown mode or type code,
+ *   num_segments outside 1 .. SEMIDETR_REF_MAX_SEGMENTS, scale or embed with more than one segment, levels outside
+ *   1 .. SEMIDETR_REF_MAX_LEVELS with valid_ratios (or != 0 without), embed without valid_ratios or dim_t, rows0 or rows1 < 1, a
+ *   NULL operand the mode reads, an out_type torch's promotion would not give, a negative stride, a misaligned pointer (element
+ *   size; 16 bytes for embed, g_embed and dim_t), eps NaN or negative.  SEMIDETR_E_TOOLARGE: rows0 * rows1 * 128 * width >= 2^31.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_REF_MAX_SEGMENTS 8
+#define SEMIDETR_REF_MAX_LEVELS 8
+#define SEMIDETR_REF_NONE 0
+#define SEMIDETR_REF_SIGMOID 1
+#define SEMIDETR_REF_REFINE 2
+typedef struct semidetr_ref_segment {
+    int rows0, rows1;
+    const void *delta, *ref;                              /* (rows0, rows1, width) through the strides below */
+    int64_t delta_stride[2], ref_stride[2];               /* in elements */
+    void *new_ref;                                        /* forward: written; backward: read */
+    int64_t new_ref_stride[2];
+    const void *g_new;                                    /* backward: upstream gradient of new_ref, or NULL */
+    int64_t g_new_stride[2];
+    void *g_delta, *g_ref;                                /* backward: written, contiguous; NULL = not wanted */
+} semidetr_ref_segment;
+typedef struct semidetr_ref_points {
+    int width, mode, num_segments, levels;                /* mode: SEMIDETR_REF_*; levels == 0 without valid_ratios */
+    float eps;
+    int delta_type, ref_type, out_type;                   /* SEMIDETR_ROW_* */
+    const float *valid_ratios;                            /* (rows1, levels, 2), or NULL: no scale, no embed */
+    const float *dim_t;                                   /* 128 divisors of the embed */
+    float *ref_input;                                     /* forward: written, (rows1, rows0, levels, width) */
+    float *embed;                                         /* forward: written, (rows0, rows1, 128 * width), or NULL */
+    const float *g_ref_input, *g_embed;                   /* backward: upstream gradients, each may be NULL */
+    semidetr_ref_segment segment[SEMIDETR_REF_MAX_SEGMENTS];
+} semidetr_ref_points;
+int semidetr_ref_points_forward(void *stream, const semidetr_ref_points *params /* host */);
+int semidetr_ref_points_backward(void *stream, const semidetr_ref_points *params /* host */);
+
 #ifdef __cplusplus
 }
 #endif

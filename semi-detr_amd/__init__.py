@@ -36,6 +36,8 @@ from .add_norm import (AddLayerNormFunction, LayerNorm, add_layer_norm, convert_
                        encoder_layer_forward)
 from .input_proj import (GroupNormTokensFunction, group_norm_to_tokens, group_norm_tokens_backward,  # noqa: E402,F401
                          group_norm_tokens_forward, project_pyramid)
+from .ref_points import (RefPointsFunction, box_outputs, decoder_forward, gen_sineembed_for_position,  # noqa: E402,F401
+                         reference_inputs, refine_boxes)
 from .pseudo_label import (filter_pseudo_labels, get_bboxes_for_pseudo_label, teacher_pseudo_labels,  # noqa: E402,F401
                            transform_bboxes)
 
@@ -51,4 +53,5 @@ __all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttnMix
            "add_layer_norm", "AddLayerNormFunction", "LayerNorm", "convert_layer_norms", "encoder_layer_forward", "encoder_forward",
            "decoder_layer_forward", "decoder_layer_forward_sa", "decoder_layer_forward_ca", "decoder_layer_forward_ffn",
            "group_norm_tokens_forward", "group_norm_tokens_backward", "GroupNormTokensFunction", "group_norm_to_tokens",
-           "project_pyramid"]
+           "project_pyramid", "gen_sineembed_for_position", "refine_boxes", "reference_inputs", "decoder_forward", "box_outputs",
+           "RefPointsFunction"]

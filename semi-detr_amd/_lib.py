@@ -128,12 +128,31 @@ class GnTokens(ctypes.Structure):
                 + _f(_STRIDE2, "pos_stride gy_stride gq_stride") + _f(c_void_p, "mean rstd") + _f(c_int, "x_type out_type pos_type"))
 
 
+# the segment table of semidetr_ref_points: SEMIDETR_REF_MAX_SEGMENTS entries, SEMIDETR_REF_MAX_LEVELS valid-ratio levels, and the
+# SEMIDETR_REF_* modes (tests/test_ref_points_ref.py reads the macros back from the header)
+REF_MAX_SEGMENTS, REF_MAX_LEVELS = 8, 8
+REF_MODES = {"SEMIDETR_REF_NONE": 0, "SEMIDETR_REF_SIGMOID": 1, "SEMIDETR_REF_REFINE": 2}
+
+
+class RefSegment(ctypes.Structure):
+    _fields_ = (_f(c_int, "rows0 rows1") + _f(c_void_p, "delta ref") + _f(_STRIDE2, "delta_stride ref_stride")
+                + _f(c_void_p, "new_ref") + _f(_STRIDE2, "new_ref_stride") + _f(c_void_p, "g_new") + _f(_STRIDE2, "g_new_stride")
+                + _f(c_void_p, "g_delta g_ref"))
+
+
+class RefPoints(ctypes.Structure):
+    _fields_ = (_f(c_int, "width mode num_segments levels") + _f(c_float, "eps") + _f(c_int, "delta_type ref_type out_type")
+                + _f(c_void_p, "valid_ratios dim_t ref_input embed g_ref_input g_embed")
+                + _f(RefSegment * REF_MAX_SEGMENTS, "segment"))
+
+
 # C struct -> mirror, in the header's order
 STRUCTS = {"semidetr_cost_params": CostParams, "semidetr_set_loss_segment": SetLossSegment, "semidetr_dn_layout": DnLayout,
            "semidetr_dn_build": DnBuild, "semidetr_dn_consistency": DnConsistency, "semidetr_consis_layer": ConsisLayer,
            "semidetr_consis_loss": ConsisLoss, "semidetr_self_attn": SelfAttn, "semidetr_self_attn_h16": SelfAttnH16,
            "semidetr_add_norm": AddNorm,
-           "semidetr_add_norm_mixed": AddNormMixed, "semidetr_gn_tokens": GnTokens}
+           "semidetr_add_norm_mixed": AddNormMixed, "semidetr_gn_tokens": GnTokens,
+           "semidetr_ref_segment": RefSegment, "semidetr_ref_points": RefPoints}
 _SEGS, _WORK = POINTER(SetLossSegment), [c_void_p, c_size_t]        # a segment table; the (workspace, workspace_bytes) pair
 
 _MSDA_FWD = [c_void_p] * 6 + [c_int] * 7 + [c_void_p]
@@ -230,6 +249,9 @@ SIGNATURES = {
     "semidetr_gn_tokens_workspace_bytes": (c_size_t, [POINTER(GnTokens), c_int]),
     "semidetr_gn_tokens_forward": (c_int, [c_void_p, POINTER(GnTokens)] + _WORK),
     "semidetr_gn_tokens_backward": (c_int, [c_void_p, POINTER(GnTokens)] + _WORK),
+    # reference-point chain of the decoder: refine, valid-ratio scaling, sine embed (ref_points.py)
+    "semidetr_ref_points_forward": (c_int, [c_void_p, POINTER(RefPoints)]),
+    "semidetr_ref_points_backward": (c_int, [c_void_p, POINTER(RefPoints)]),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so
