@@ -394,6 +394,36 @@ int semidetr_build_targets(void *stream, const int64_t *assigned_gt_inds, const 
                            int num_problems, int num_query, int64_t num_classes, int64_t *labels,
                            float *label_weights, float *bbox_targets, float *bbox_weights, int32_t *num_pos);
 
+/* The three calls above as ONE call that needs no staging: cost, then assignment, then (where asked) the training targets, back
+ * to back on `stream`.  The ground truths stay where the caller has them: problem b reads boxes[b] ((count[b], 4) fp32
+ * contiguous, 16-byte aligned) and labels[b] ((count[b],) int64) through the table below, which travels BY VALUE in the kernel
+ * arguments together with the exclusive offsets and the image sizes -- no device allocation, no copy command, and the launch has
+ * copied the block when the call returns (nothing has to outlive it but the tensors the pointers name, until the kernels ran).
+ * Same kernels, same arithmetic and same outputs as the three calls on the concatenated ground truths.
+ *   SEMIDETR_MATCH_TABLE = 64 problems: sizeof(semidetr_match_table) = 2056 bytes, and the largest argument block of the three
+ *   kernels (the assignment's) is 2136 bytes of the 4096 the HIP runtime accepts for one launch.  (A loss() call of the benchmark
+ *   has 28 problems, one of the warm-up stage 35; callers with more take the three calls above.)
+ *   table (host): num_problems in [1, SEMIDETR_MATCH_TABLE]; offsets[b] = sum of count[:b], offsets[num_problems] = total;
+ *       img_wh[b] = (img_w, img_h); entries past num_problems are ignored; boxes[b] / labels[b] may be NULL where count[b] == 0.
+ *   cost (Q * total) fp32 as laid out above; match_row .. workspace as semidetr_lsap_solve takes them.
+ *   target_labels NULL: no targets.  Otherwise target_labels .. num_pos as semidetr_build_targets' labels .. num_pos, and
+ *   assigned_gt_inds is required. */
+#define SEMIDETR_MATCH_TABLE 64
+typedef struct semidetr_match_table {
+    int num_problems;
+    int32_t count[SEMIDETR_MATCH_TABLE];
+    int32_t offsets[SEMIDETR_MATCH_TABLE + 1];
+    float img_wh[SEMIDETR_MATCH_TABLE][2];
+    const float *boxes[SEMIDETR_MATCH_TABLE];
+    const int64_t *labels[SEMIDETR_MATCH_TABLE];
+} semidetr_match_table;
+int semidetr_hungarian_assign_f32(void *stream, const float *bbox_pred, const float *cls_pred,
+                                  const semidetr_match_table *table /* host */, int num_query, int num_classes,
+                                  const semidetr_cost_params *params /* host */, float *cost, int64_t *match_row,
+                                  int64_t *match_col, int64_t *assigned_gt_inds, int64_t *assigned_labels, int32_t *status,
+                                  void *workspace, int64_t target_num_classes, int64_t *target_labels, float *label_weights,
+                                  float *bbox_targets, float *bbox_weights, int32_t *num_pos);
+
 /* ---------------------------------------------------------------------------------------------
  * Mean-teacher EMA, one launch for the whole parameter list.
  *
@@ -465,6 +495,41 @@ int semidetr_pseudo_nms_f32(void *stream, const float *cls_logits, const float *
 int semidetr_transform_bboxes_f32(void *stream, const float *boxes, int box_stride, const int32_t *box_offsets,
                                   const int32_t *box_counts, int num_images, int max_boxes_per_image,
                                   const float *matrices, const float *out_hw, float *out_boxes);
+
+/* The teacher's chain semidetr_pseudo_nms_f32 -> semidetr_pseudo_label_filter_f32 as ONE call, and the warp in a form that reads
+ * every image's boxes where they are; the small per-image arguments travel BY VALUE in the kernel arguments (no device
+ * allocation, no copy command; the launch has copied the block when the call returns).  Same kernels and same bits as the calls
+ * above.  SEMIDETR_IMAGE_TABLE = 64 images: sizeof(semidetr_image_sizes) = 516 and sizeof(semidetr_box_table) = 2312 bytes of the
+ * 4096 bytes of kernel arguments the HIP runtime accepts for one launch; callers with more images take the calls above.
+ *   semidetr_teacher_pseudo_labels_f32: img_hw (host) holds num_images in [1, SEMIDETR_IMAGE_TABLE] and (height, width) per image.
+ *       The filter reads the NMS's padded output (image b's rows start at b * max_per_img).  counts (2, B) int32: row 0 the NMS's
+ *       out_count, row 1 the filter's -- one buffer for the one read-back.  out_dets / out_det_labels as semidetr_pseudo_nms_f32's
+ *       out_dets / out_labels; out_boxes (B * max_per_img, 4), out_labels, out_scores (B * max_per_img,), out_thr (B,) as the
+ *       filter's.
+ *   semidetr_transform_bboxes_table_f32: table (host): image b has count[b] boxes, rows of box_stride[b] (>= 4) floats at boxes[b]
+ *       (x1,y1,x2,y2 first), its (3,3) row-major fp32 matrix at matrix[b] (DEVICE pointers), out_hw[b] = (h, w) of the target
+ *       image, and its warped boxes go to rows [out_offset[b], +count[b]) of out_boxes (rows of 4 floats).  boxes[b] / matrix[b] may
+ *       be NULL where count[b] == 0. */
+#define SEMIDETR_IMAGE_TABLE 64
+typedef struct semidetr_image_sizes {
+    int num_images;
+    float hw[SEMIDETR_IMAGE_TABLE][2];
+} semidetr_image_sizes;
+typedef struct semidetr_box_table {
+    int num_images;
+    int32_t count[SEMIDETR_IMAGE_TABLE];
+    int32_t box_stride[SEMIDETR_IMAGE_TABLE];
+    int32_t out_offset[SEMIDETR_IMAGE_TABLE];
+    float out_hw[SEMIDETR_IMAGE_TABLE][2];
+    const float *boxes[SEMIDETR_IMAGE_TABLE];
+    const float *matrix[SEMIDETR_IMAGE_TABLE];
+} semidetr_box_table;
+int semidetr_teacher_pseudo_labels_f32(void *stream, const float *cls_logits, const float *bbox_pred,
+                                       const semidetr_image_sizes *img_hw /* host */, int num_query, int num_classes,
+                                       float score_thr, float iou_thr, int max_per_img, void *workspace, size_t workspace_bytes,
+                                       float *out_dets, int64_t *out_det_labels, float *out_boxes, int64_t *out_labels,
+                                       float *out_scores, int32_t *counts, float *out_thr);
+int semidetr_transform_bboxes_table_f32(void *stream, const semidetr_box_table *table /* host */, float *out_boxes);
 
 /* ---------------------------------------------------------------------------------------------
  * One-to-many (task-aligned) assigner of the warm-up stage + its training targets (SURVEY.md section 8(f)

@@ -51,6 +51,30 @@ class CostParams(ctypes.Structure):
                 + _f(c_int, "iou_giou pred_xyxy"))
 
 
+# the ground-truth table of semidetr_hungarian_assign_f32: SEMIDETR_MATCH_TABLE problems, by value in the kernel arguments
+# (tests/test_native_chains_host.py reads the macro back from the header)
+MATCH_TABLE = 64
+
+
+class MatchTable(ctypes.Structure):
+    _fields_ = (_f(c_int, "num_problems") + _f(ctypes.c_int32 * MATCH_TABLE, "count") + _f(ctypes.c_int32 * (MATCH_TABLE + 1), "offsets")
+                + _f(c_float * 2 * MATCH_TABLE, "img_wh") + _f(c_void_p * MATCH_TABLE, "boxes labels"))
+
+
+# the per-image tables of semidetr_teacher_pseudo_labels_f32 / semidetr_transform_bboxes_table_f32: SEMIDETR_IMAGE_TABLE images
+IMAGE_TABLE = 64
+_IMG_I32 = ctypes.c_int32 * IMAGE_TABLE
+
+
+class ImageSizes(ctypes.Structure):
+    _fields_ = _f(c_int, "num_images") + _f(c_float * 2 * IMAGE_TABLE, "hw")
+
+
+class BoxTable(ctypes.Structure):
+    _fields_ = (_f(c_int, "num_images") + _f(_IMG_I32, "count box_stride out_offset") + _f(c_float * 2 * IMAGE_TABLE, "out_hw")
+                + _f(c_void_p * IMAGE_TABLE, "boxes matrix"))
+
+
 class SetLossSegment(ctypes.Structure):
     _fields_ = (_f(c_int, "kind num_layers num_images num_query num_classes")
                 + _f(c_void_p, "logits") + _f(c_int64 * 3, "logit_stride") + _f(c_void_p, "boxes") + _f(c_int64 * 3, "box_stride")
@@ -147,7 +171,8 @@ class RefPoints(ctypes.Structure):
 
 
 # C struct -> mirror, in the header's order
-STRUCTS = {"semidetr_cost_params": CostParams, "semidetr_set_loss_segment": SetLossSegment, "semidetr_dn_layout": DnLayout,
+STRUCTS = {"semidetr_cost_params": CostParams, "semidetr_match_table": MatchTable, "semidetr_image_sizes": ImageSizes,
+           "semidetr_box_table": BoxTable, "semidetr_set_loss_segment": SetLossSegment, "semidetr_dn_layout": DnLayout,
            "semidetr_dn_build": DnBuild, "semidetr_dn_consistency": DnConsistency, "semidetr_consis_layer": ConsisLayer,
            "semidetr_consis_loss": ConsisLoss, "semidetr_self_attn": SelfAttn, "semidetr_self_attn_h16": SelfAttnH16,
            "semidetr_add_norm": AddNorm,
@@ -195,6 +220,9 @@ SIGNATURES = {
     "semidetr_lsap_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "semidetr_lsap_solve": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6),
     "semidetr_build_targets": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int64] + [c_void_p] * 5),
+    # ... the three as one call, the ground truths through a by-value table
+    "semidetr_hungarian_assign_f32": (c_int, [c_void_p] * 3 + [POINTER(MatchTable), c_int, c_int, POINTER(CostParams)]
+                                      + [c_void_p] * 7 + [c_int64] + [c_void_p] * 5),
     "semidetr_ema_multi_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_double]),
     "semidetr_ema_flat_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double]),
     "semidetr_pseudo_label_filter_f32": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 6),
@@ -205,6 +233,10 @@ SIGNATURES = {
     "semidetr_tal_loss_workspace_bytes": (c_size_t, []),
     "semidetr_tal_loss_f32": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_float, c_int] + [c_void_p] * 3),
     "semidetr_transform_bboxes_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3),
+    # ... the teacher's chain as one call and the warp through a pointer table, the small arguments by value
+    "semidetr_teacher_pseudo_labels_f32": (c_int, [c_void_p] * 3 + [POINTER(ImageSizes), c_int, c_int, c_float, c_float, c_int,
+                                                    c_void_p, c_size_t] + [c_void_p] * 7),
+    "semidetr_transform_bboxes_table_f32": (c_int, [c_void_p, POINTER(BoxTable), c_void_p]),
     "semidetr_gmm_match_costs_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 2),
     "semidetr_gmm_fit_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 3 + [c_double, c_double, c_int]
                              + [c_void_p] * 4),

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "match_table.h"
 
 #pragma clang fp contract(off)
 
@@ -96,16 +97,16 @@ __host__ __device__ inline size_t lsap_bytes(int ncmax, int nrmax)
 
 // COST_LDS: the problem's cost block is copied into LDS (while it is checked for NaN / -inf) and the searches read
 // it from there -- every Dijkstra step otherwise waits for a dependent batch of global loads.
-template <bool USE_LDS, bool COST_LDS = false>
+// GT: where problem b's count, offset and labels are (match_table.h); the cost-only caller's labels may be NULL
+template <class GT, bool USE_LDS, bool COST_LDS = false>
 __global__ __launch_bounds__(64) void lsap_kernel(
-    const float *__restrict__ cost, const int32_t *__restrict__ gt_offsets,
-    const int64_t *__restrict__ gt_labels, int Q, int ncmax, int nrmax, int64_t *__restrict__ match_row,
+    const float *__restrict__ cost, const GT gts, int Q, int ncmax, int nrmax, int64_t *__restrict__ match_row,
     int64_t *__restrict__ match_col, int64_t *__restrict__ gt_inds, int64_t *__restrict__ labels,
     int32_t *__restrict__ status, char *__restrict__ ws, size_t ws_stride)
 {
     extern __shared__ double smem_d[];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int g0 = gt_offsets[b], G = gt_offsets[b + 1] - g0;
+    const int g0 = gts.start(b), G = gts.count(b);
 
     // defaults of the scatter: every prediction background (hungarian_assigner.py:142 / :108-114)
     for (int q = lane; q < Q; q += 64) {
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(64) void lsap_kernel(
     if (G <= 0 || Q <= 0) return;
 
     int po = 0;   // where this problem's (row, col) pairs start
-    for (int bb = lane; bb < b; bb += 64) po += min(Q, gt_offsets[bb + 1] - gt_offsets[bb]);
+    for (int bb = lane; bb < b; bb += 64) po += min(Q, gts.count(bb));
     po = wave_sum_i(po);
 
     const bool tr = G < Q;                        // scipy solves the transposed problem when nc < nr
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(64) void lsap_kernel(
         if (match_row) match_row[po + rank] = q;
         if (match_col) match_col[po + rank] = g;
         if (gt_inds) gt_inds[(int64_t)b * Q + q] = g + 1;
-        if (labels) labels[(int64_t)b * Q + q] = gt_labels[g0 + g];
+        if (labels) labels[(int64_t)b * Q + q] = gts.labels(b)[g];
     }
 }
 
@@ -278,10 +279,9 @@ constexpr size_t kLdsBig = 150 * 1024;      // with the cost block; one problem 
 //   labels = num_classes (background) except labels[pos] = gt_labels[gt_inds[pos]-1]; label_weights = 1;
 //   bbox_targets[pos] = cxcywh(gt_bboxes[gt_inds[pos]-1] / (w,h,w,h)); bbox_weights[pos] = 1; num_pos per problem.
 #pragma clang fp contract(off)
+template <class GT>
 __global__ __launch_bounds__(256) void build_targets_kernel(
-    const int64_t *__restrict__ gt_inds, const float *__restrict__ gt_bboxes, const int64_t *__restrict__ gt_labels,
-    const int32_t *__restrict__ gt_offsets, const float *__restrict__ img_wh, int Q, int64_t num_classes,
-    int64_t *__restrict__ labels, float *__restrict__ label_weights, float *__restrict__ bbox_targets,
+    const int64_t *__restrict__ gt_inds, const GT gts, int Q, int64_t num_classes, int64_t *__restrict__ labels, float *__restrict__ label_weights, float *__restrict__ bbox_targets,
     float *__restrict__ bbox_weights, int32_t *__restrict__ num_pos)
 {
     const int b = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
@@ -293,12 +293,12 @@ __global__ __launch_bounds__(256) void build_targets_kernel(
         float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
         int64_t lab = num_classes;
         if (pos) {
-            const int64_t g = gt_offsets[b] + gi - 1;
-            const float4 bx = *reinterpret_cast<const float4 *>(gt_bboxes + g * 4);
-            const float w = img_wh[2 * b], h = img_wh[2 * b + 1];
+            const int64_t g = gi - 1;
+            const float4 bx = *reinterpret_cast<const float4 *>(gts.boxes(b) + g * 4);
+            const float w = gts.img_w(b), h = gts.img_h(b);
             const float x1 = bx.x / w, y1 = bx.y / h, x2 = bx.z / w, y2 = bx.w / h;
             t = make_float4((x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1);
-            lab = gt_labels[g];
+            lab = gts.labels(b)[g];
         }
         labels[o] = lab;
         label_weights[o] = 1.f;
@@ -308,6 +308,49 @@ __global__ __launch_bounds__(256) void build_targets_kernel(
     }
     const int n = __popcll(__ballot(pos));
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(&num_pos[b], n);
+}
+
+// num_pos is zeroed, then counted by the kernel
+template <class GT>
+int launch_build_targets(hipStream_t st, const int64_t *assigned_gt_inds, const GT &gts, int num_problems, int num_query,
+                         int64_t num_classes, int64_t *labels, float *label_weights, float *bbox_targets, float *bbox_weights,
+                         int32_t *num_pos)
+{
+    hipError_t e = hipMemsetAsync(num_pos, 0, sizeof(int32_t) * (size_t)num_problems, st);
+    if (e != hipSuccess) return semidetr::fail((int)e, "build_targets memset: %s", hipGetErrorString(e));
+    if (num_query == 0) return SEMIDETR_OK;
+    hipLaunchKernelGGL(build_targets_kernel<GT>, dim3((num_query + 255) / 256, num_problems), dim3(256), 0, st,
+                       assigned_gt_inds, gts, num_query, num_classes, labels, label_weights, bbox_targets, bbox_weights, num_pos);
+    return semidetr::launch_status("build_targets_kernel");
+}
+
+// the LDS tier of a launch and the launch itself, for either ground-truth source
+template <class GT>
+int launch_lsap(hipStream_t st, const float *cost, const GT &gts, int num_problems, int num_query, int max_gt,
+                int64_t *match_row, int64_t *match_col, int64_t *assigned_gt_inds, int64_t *assigned_labels, int32_t *status,
+                void *workspace)
+{
+    const int ncmax = num_query > max_gt ? num_query : max_gt;
+    const int nrmax = num_query < max_gt ? num_query : max_gt;
+    const size_t per = lsap_bytes(ncmax > 0 ? ncmax : 1, nrmax > 0 ? nrmax : 1);
+    const size_t cost_bytes = (size_t)max_gt * (size_t)num_query * sizeof(float);
+    if (per <= kLdsLimit && per + cost_bytes <= kLdsBig) {         // solver state AND the cost block in LDS
+        if (int rc = semidetr::allow_big_lds(&lsap_kernel<GT, true, true>, kLdsBig, "lsap")) return rc;
+        hipLaunchKernelGGL((lsap_kernel<GT, true, true>), dim3(num_problems), dim3(64), per + cost_bytes, st, cost, gts,
+                           num_query, ncmax, nrmax, match_row, match_col, assigned_gt_inds,
+                           assigned_labels, status, (char *)nullptr, (size_t)0);
+    } else if (per <= kLdsLimit) {
+        hipLaunchKernelGGL((lsap_kernel<GT, true>), dim3(num_problems), dim3(64), per, st, cost, gts,
+                           num_query, ncmax, nrmax, match_row, match_col, assigned_gt_inds,
+                           assigned_labels, status, (char *)nullptr, (size_t)0);
+    } else {
+        SEMIDETR_REQUIRE(workspace, SEMIDETR_E_BADARG, "lsap: workspace of %lld bytes required",
+                         (long long)(per * (size_t)num_problems));
+        hipLaunchKernelGGL((lsap_kernel<GT, false>), dim3(num_problems), dim3(64), 0, st, cost, gts,
+                           num_query, ncmax, nrmax, match_row, match_col, assigned_gt_inds,
+                           assigned_labels, status, (char *)workspace, per);
+    }
+    return semidetr::launch_status("lsap_kernel");
 }
 
 }  // namespace
@@ -334,28 +377,9 @@ extern "C" int semidetr_lsap_solve(void *stream, const float *cost, const int32_
     SEMIDETR_REQUIRE(gt_offsets && status, SEMIDETR_E_BADARG, "lsap: null gt_offsets/status");
     SEMIDETR_REQUIRE(total_gt == 0 || num_query == 0 || cost, SEMIDETR_E_BADARG, "lsap: null cost");
     SEMIDETR_REQUIRE(!assigned_labels || total_gt == 0 || gt_labels, SEMIDETR_E_BADARG, "lsap: null gt_labels");
-    const int ncmax = num_query > max_gt ? num_query : max_gt;
-    const int nrmax = num_query < max_gt ? num_query : max_gt;
-    const size_t per = lsap_bytes(ncmax > 0 ? ncmax : 1, nrmax > 0 ? nrmax : 1);
-    hipStream_t st = semidetr::as_stream(stream);
-    const size_t cost_bytes = (size_t)max_gt * (size_t)num_query * sizeof(float);
-    if (per <= kLdsLimit && per + cost_bytes <= kLdsBig) {         // solver state AND the cost block in LDS
-        if (int rc = semidetr::allow_big_lds(&lsap_kernel<true, true>, kLdsBig, "lsap")) return rc;
-        hipLaunchKernelGGL((lsap_kernel<true, true>), dim3(num_problems), dim3(64), per + cost_bytes, st, cost, gt_offsets,
-                           gt_labels, num_query, ncmax, nrmax, match_row, match_col, assigned_gt_inds,
-                           assigned_labels, status, (char *)nullptr, (size_t)0);
-    } else if (per <= kLdsLimit) {
-        hipLaunchKernelGGL(lsap_kernel<true>, dim3(num_problems), dim3(64), per, st, cost, gt_offsets,
-                           gt_labels, num_query, ncmax, nrmax, match_row, match_col, assigned_gt_inds,
-                           assigned_labels, status, (char *)nullptr, (size_t)0);
-    } else {
-        SEMIDETR_REQUIRE(workspace, SEMIDETR_E_BADARG, "lsap: workspace of %lld bytes required",
-                         (long long)(per * (size_t)num_problems));
-        hipLaunchKernelGGL(lsap_kernel<false>, dim3(num_problems), dim3(64), 0, st, cost, gt_offsets,
-                           gt_labels, num_query, ncmax, nrmax, match_row, match_col, assigned_gt_inds,
-                           assigned_labels, status, (char *)workspace, per);
-    }
-    return semidetr::launch_status("lsap_kernel");
+    const semidetr::FlatGt gts = {nullptr, gt_labels, gt_offsets, nullptr};
+    return launch_lsap(semidetr::as_stream(stream), cost, gts, num_problems, num_query, max_gt, match_row, match_col,
+                       assigned_gt_inds, assigned_labels, status, workspace);
 }
 
 extern "C" int semidetr_build_targets(void *stream, const int64_t *assigned_gt_inds, const float *gt_bboxes,
@@ -370,12 +394,23 @@ extern "C" int semidetr_build_targets(void *stream, const int64_t *assigned_gt_i
                          bbox_weights && num_pos,
                      SEMIDETR_E_BADARG, "build_targets: null pointer argument");
     SEMIDETR_REQUIRE(num_problems <= 65535, SEMIDETR_E_TOOLARGE, "build_targets: more than 65535 problems");
-    hipStream_t st = semidetr::as_stream(stream);
-    hipError_t e = hipMemsetAsync(num_pos, 0, sizeof(int32_t) * (size_t)num_problems, st);
-    if (e != hipSuccess) return semidetr::fail((int)e, "build_targets memset: %s", hipGetErrorString(e));
-    if (num_query == 0) return SEMIDETR_OK;
-    hipLaunchKernelGGL(build_targets_kernel, dim3((num_query + 255) / 256, num_problems), dim3(256), 0, st,
-                       assigned_gt_inds, gt_bboxes, gt_labels, gt_offsets, img_wh, num_query, num_classes, labels,
-                       label_weights, bbox_targets, bbox_weights, num_pos);
-    return semidetr::launch_status("build_targets_kernel");
+    const semidetr::FlatGt gts = {gt_bboxes, gt_labels, gt_offsets, img_wh};
+    return launch_build_targets(semidetr::as_stream(stream), assigned_gt_inds, gts, num_problems, num_query, num_classes, labels,
+                                label_weights, bbox_targets, bbox_weights, num_pos);
+}
+
+int semidetr::launch_lsap_table(hipStream_t st, const float *cost, const semidetr_match_table &table, int num_query, int max_gt,
+                                int64_t *match_row, int64_t *match_col, int64_t *assigned_gt_inds, int64_t *assigned_labels,
+                                int32_t *status, void *workspace)
+{
+    return launch_lsap(st, cost, semidetr::TableGt{table}, table.num_problems, num_query, max_gt, match_row, match_col,
+                       assigned_gt_inds, assigned_labels, status, workspace);
+}
+
+int semidetr::launch_build_targets_table(hipStream_t st, const int64_t *assigned_gt_inds, const semidetr_match_table &table,
+                                         int num_query, int64_t num_classes, int64_t *labels, float *label_weights,
+                                         float *bbox_targets, float *bbox_weights, int32_t *num_pos)
+{
+    return launch_build_targets(st, assigned_gt_inds, semidetr::TableGt{table}, table.num_problems, num_query, num_classes, labels,
+                                label_weights, bbox_targets, bbox_weights, num_pos);
 }

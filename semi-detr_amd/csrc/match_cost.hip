@@ -5,7 +5,9 @@
 // .../match_costs/match_cost.py:33-50 (BBoxL1Cost), :83-99 (FocalLossCost), :169-185 (IoUCost),
 // .../iou_calculators/iou2d_calculator.py:200-261 (bbox_overlaps), .../transforms.py:222-247.
 // The reference builds the matrix with ~30 small elementwise launches per problem; here one thread owns
-// one prediction, keeps its box in registers and walks the problem's ground truths.  The matrix is
+// one prediction, keeps its box in registers and takes every gridDim.z-th ground truth of the problem (one
+// ground truth per thread up to kGtSlices of them: the walk over 15 ground truths, two transcendentals deep
+// each, was a serial chain in a launch that fills a fraction of the chip).  The matrix is
 // written TRANSPOSED ((G_b, Q) row-major, see semidetr_hip.h) so the stores are coalesced along Q and
 // the assignment kernel -- which always solves the transposed problem when Q > G -- streams rows.
 //
@@ -14,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "match_table.h"
 
 #pragma clang fp contract(off)
 
@@ -24,17 +27,19 @@ __device__ __forceinline__ float pow_gamma(float x, float gamma)
     return gamma == 2.0f ? x * x : powf(x, gamma);   // torch.pow(x, 2) is x*x as well
 }
 
+// GT: where problem b's ground truths are (match_table.h)
+template <class GT>
 __global__ __launch_bounds__(256) void match_cost_kernel(
-    const float *__restrict__ bbox_pred, const float *__restrict__ cls_pred,
-    const float *__restrict__ gt_bboxes, const int64_t *__restrict__ gt_labels,
-    const int32_t *__restrict__ gt_offsets, const float *__restrict__ img_wh, int Q, int C,
+    const float *__restrict__ bbox_pred, const float *__restrict__ cls_pred, const GT gts, int Q, int C,
     semidetr_cost_params prm, float *__restrict__ cost)
 {
     const int b = blockIdx.y;
-    const int g0 = gt_offsets[b], G = gt_offsets[b + 1] - g0;
+    const int g0 = gts.start(b), G = gts.count(b);
     const int q = blockIdx.x * 256 + threadIdx.x;
-    if (G <= 0 || q >= Q) return;
-    const float img_w = img_wh[2 * b], img_h = img_wh[2 * b + 1];
+    if (G <= (int)blockIdx.z || q >= Q) return;
+    const float img_w = gts.img_w(b), img_h = gts.img_h(b);
+    const float *__restrict__ gt_bboxes = gts.boxes(b);
+    const int64_t *__restrict__ gt_labels = gts.labels(b);
     const float4 bp = *reinterpret_cast<const float4 *>(bbox_pred + ((int64_t)b * Q + q) * 4);
     float cx = bp.x, cy = bp.y, bw = bp.z, bh = bp.w;
     // bbox_cxcywh_to_xyxy then * factor
@@ -47,9 +52,9 @@ __global__ __launch_bounds__(256) void match_cost_kernel(
     const float area1 = (x1 - x0) * (y1 - y0);
     const float *cls_row = cls_pred + ((int64_t)b * Q + q) * C;
     float *out = cost + (int64_t)Q * g0 + q;
-    for (int j = 0; j < G; ++j) {
-        const float4 gt = *reinterpret_cast<const float4 *>(gt_bboxes + (int64_t)(g0 + j) * 4);
-        const int label = (int)gt_labels[g0 + j];
+    for (int j = blockIdx.z; j < G; j += gridDim.z) {
+        const float4 gt = *reinterpret_cast<const float4 *>(gt_bboxes + (int64_t)j * 4);
+        const int label = (int)gt_labels[j];
         // --- FocalLossCost
         // a label outside [0, C) is an index error in the reference (match_cost.py:96); here it must neither read out
         // of bounds nor pass silently: the cost becomes NaN, which the LSAP status word reports (ValueError)
@@ -86,6 +91,14 @@ __global__ __launch_bounds__(256) void match_cost_kernel(
     }
 }
 
+// ground truths of a problem spread over the grid's z dimension (every element is computed by the same instructions
+// wherever it lands, so the slicing does not show in the result)
+constexpr int kGtSlices = 16;
+inline dim3 cost_grid(int num_query, int num_problems, int64_t most_gt)
+{
+    return dim3((num_query + 255) / 256, num_problems, (unsigned)(most_gt < kGtSlices ? (most_gt > 0 ? most_gt : 1) : kGtSlices));
+}
+
 }  // namespace
 
 extern "C" int semidetr_match_cost_f32(void *stream, const float *bbox_pred, const float *cls_pred,
@@ -105,9 +118,21 @@ extern "C" int semidetr_match_cost_f32(void *stream, const float *bbox_pred, con
     SEMIDETR_REQUIRE((int64_t)num_query * total_gt < INT32_MAX, SEMIDETR_E_TOOLARGE, "match_cost: matrix too large");
     SEMIDETR_REQUIRE((((uintptr_t)bbox_pred | (uintptr_t)gt_bboxes) & 15) == 0, SEMIDETR_E_BADARG,
                      "match_cost: bbox_pred / gt_bboxes must be 16-byte aligned");
-    const dim3 grid((num_query + 255) / 256, num_problems);
-    hipLaunchKernelGGL(match_cost_kernel, grid, dim3(256), 0, semidetr::as_stream(stream), bbox_pred,
-                       cls_pred, gt_bboxes, gt_labels, gt_offsets, img_wh, num_query, num_classes, *params,
-                       cost);
+    const dim3 grid = cost_grid(num_query, num_problems, total_gt);      // (no problem has more than total_gt)
+    const semidetr::FlatGt gts = {gt_bboxes, gt_labels, gt_offsets, img_wh};
+    hipLaunchKernelGGL(match_cost_kernel<semidetr::FlatGt>, grid, dim3(256), 0, semidetr::as_stream(stream), bbox_pred,
+                       cls_pred, gts, num_query, num_classes, *params, cost);
+    return semidetr::launch_status("match_cost_kernel");
+}
+
+int semidetr::launch_match_cost_table(hipStream_t st, const float *bbox_pred, const float *cls_pred,
+                                      const semidetr_match_table &table, int num_query, int num_classes,
+                                      const semidetr_cost_params &params, float *cost)
+{
+    int most_gt = 0;
+    for (int b = 0; b < table.num_problems; ++b) most_gt = table.count[b] > most_gt ? table.count[b] : most_gt;
+    const dim3 grid = cost_grid(num_query, table.num_problems, most_gt);
+    hipLaunchKernelGGL(match_cost_kernel<semidetr::TableGt>, grid, dim3(256), 0, st, bbox_pred, cls_pred,
+                       semidetr::TableGt{table}, num_query, num_classes, params, cost);
     return semidetr::launch_status("match_cost_kernel");
 }

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "pseudo_chain.h"
 
 #pragma clang fp contract(off)      // every result is one rounded operation, like the reference's separate torch ops
 
@@ -90,14 +91,14 @@ inline Workspace carve(void *ws, int B, int Q, int C)
 // so the running maximum is an integer atomic max on the float's bits, one per workgroup (the slot is zeroed by
 // the launcher together with count).
 constexpr int kPrepQueries = 16;
+template <class HW>      // where the image sizes are (pseudo_chain.h)
 __global__ __launch_bounds__(256) void nms_prepare_kernel(const float *__restrict__ logits,
-                                                          const float *__restrict__ bbox_pred,
-                                                          const float *__restrict__ img_hw, int Q, int C,
+                                                          const float *__restrict__ bbox_pred, const HW hw, int Q, int C,
                                                           float score_thr, Workspace ws)
 {
     __shared__ float red[4];
     const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const float img_h = img_hw[2 * b], img_w = img_hw[2 * b + 1];
+    const float img_h = hw.h(b), img_w = hw.w(b);
     float mx = 0.f;
     for (int r = wv; r < kPrepQueries; r += 4) {
         const int q = blockIdx.x * kPrepQueries + r;
@@ -298,19 +299,39 @@ __global__ __launch_bounds__(kTopThreads) void nms_topk_kernel(const float *__re
 }
 
 // ---- weak -> strong box warp: 4 corners through the 3x3 matrix, bounding box of the images, clamp
-__global__ __launch_bounds__(256) void transform_bboxes_kernel(const float *__restrict__ boxes, int box_stride,
-                                                               const int32_t *__restrict__ offs,
-                                                               const int32_t *__restrict__ counts,
-                                                               const float *__restrict__ mats,
-                                                               const float *__restrict__ out_hw,
-                                                               float *__restrict__ out)
+// image b's boxes, matrix and target size in one batch tensor each (device offsets) ...
+struct BatchBoxes {
+    const float *boxes;
+    int box_stride;
+    const int32_t *offs, *counts;
+    const float *mats, *out_hw;
+    __device__ __forceinline__ int count(int b) const { return counts ? counts[b] : offs[b + 1] - offs[b]; }
+    __device__ __forceinline__ int out_row(int b) const { return offs[b]; }
+    __device__ __forceinline__ const float *box(int b, int i) const { return boxes + (size_t)(offs[b] + i) * box_stride; }
+    __device__ __forceinline__ const float *matrix(int b) const { return mats + 9 * b; }
+    __device__ __forceinline__ float h(int b) const { return out_hw[2 * b]; }
+    __device__ __forceinline__ float w(int b) const { return out_hw[2 * b + 1]; }
+};
+// ... or wherever the caller has them, through the by-value table of semidetr_transform_bboxes_table_f32
+struct TableBoxes {
+    semidetr_box_table t;
+    __device__ __forceinline__ int count(int b) const { return t.count[b]; }
+    __device__ __forceinline__ int out_row(int b) const { return t.out_offset[b]; }
+    __device__ __forceinline__ const float *box(int b, int i) const { return t.boxes[b] + (size_t)i * t.box_stride[b]; }
+    __device__ __forceinline__ const float *matrix(int b) const { return t.matrix[b]; }
+    __device__ __forceinline__ float h(int b) const { return t.out_hw[b][0]; }
+    __device__ __forceinline__ float w(int b) const { return t.out_hw[b][1]; }
+};
+
+template <class SRC>
+__global__ __launch_bounds__(256) void transform_bboxes_kernel(const SRC src, float *__restrict__ out)
 {
     const int b = blockIdx.y;
-    const int p0 = offs[b], K = counts ? counts[b] : offs[b + 1] - p0;
+    const int p0 = src.out_row(b), K = src.count(b);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= K) return;
-    const float *M = mats + 9 * b;
-    const float *bx = boxes + (size_t)(p0 + i) * box_stride;
+    const float *M = src.matrix(b);
+    const float *bx = src.box(b, i);
     const float px[4] = {bx[0], bx[2], bx[2], bx[0]}, py[4] = {bx[1], bx[1], bx[3], bx[3]};
     float minx = __builtin_huge_valf(), miny = minx, maxx = -minx, maxy = -minx;
 #pragma unroll
@@ -322,7 +343,7 @@ __global__ __launch_bounds__(256) void transform_bboxes_kernel(const float *__re
         minx = fminf(minx, u); maxx = fmaxf(maxx, u);
         miny = fminf(miny, v); maxy = fmaxf(maxy, v);
     }
-    const float oh = out_hw[2 * b], ow = out_hw[2 * b + 1];
+    const float oh = src.h(b), ow = src.w(b);
     float *o = out + (size_t)(p0 + i) * 4;
     o[0] = fminf(fmaxf(minx, 0.f), ow);
     o[1] = fminf(fmaxf(miny, 0.f), oh);
@@ -338,17 +359,18 @@ extern "C" size_t semidetr_nms_workspace_bytes(int batch, int num_query, int num
     return workspace_bytes(batch, num_query, num_classes);
 }
 
-extern "C" int semidetr_pseudo_nms_f32(void *stream, const float *cls_logits, const float *bbox_pred,
-                                       const float *img_hw, int batch, int num_query, int num_classes,
-                                       float score_thr, float iou_thr, int max_per_img, void *workspace,
-                                       size_t workspace_bytes_, float *out_dets, int64_t *out_labels,
-                                       int32_t *out_count)
+namespace {
+
+// the checks and the launches of the NMS for either source of the image sizes (`have_hw`: the source holds them)
+template <class HW>
+int pseudo_nms(hipStream_t st, const float *cls_logits, const float *bbox_pred, const HW &hw, bool have_hw, int batch,
+               int num_query, int num_classes, float score_thr, float iou_thr, int max_per_img, void *workspace,
+               size_t workspace_bytes_, float *out_dets, int64_t *out_labels, int32_t *out_count)
 {
     const int B = batch, Q = num_query, C = num_classes;
     SEMIDETR_REQUIRE(B >= 0 && Q >= 0 && C >= 0, SEMIDETR_E_BADARG, "pseudo_nms: negative size");
     if (B == 0) return SEMIDETR_OK;
     SEMIDETR_REQUIRE(out_count, SEMIDETR_E_BADARG, "pseudo_nms: null out_count");
-    hipStream_t st = semidetr::as_stream(stream);
     if (Q == 0 || C == 0) {
         hipError_t e = hipMemsetAsync(out_count, 0, sizeof(int32_t) * B, st);
         if (e != hipSuccess) return semidetr::fail((int)e, "pseudo_nms memset: %s", hipGetErrorString(e));
@@ -356,7 +378,7 @@ extern "C" int semidetr_pseudo_nms_f32(void *stream, const float *cls_logits, co
     }
     SEMIDETR_REQUIRE(max_per_img >= 1 && max_per_img <= kTopCap, SEMIDETR_E_BADARG,
                      "pseudo_nms: max_per_img must be in [1, %d] (got %d)", kTopCap, max_per_img);
-    SEMIDETR_REQUIRE(cls_logits && bbox_pred && img_hw && out_dets && out_labels && workspace, SEMIDETR_E_BADARG,
+    SEMIDETR_REQUIRE(cls_logits && bbox_pred && have_hw && out_dets && out_labels && workspace, SEMIDETR_E_BADARG,
                      "pseudo_nms: null pointer argument");
     SEMIDETR_REQUIRE(iou_thr >= 0.f, SEMIDETR_E_BADARG, "pseudo_nms: iou_thr must be >= 0 (got %g)", (double)iou_thr);
     SEMIDETR_REQUIRE(Q <= 2048, SEMIDETR_E_TOOLARGE, "pseudo_nms: at most 2048 queries per image (got %d)", Q);
@@ -369,8 +391,8 @@ extern "C" int semidetr_pseudo_nms_f32(void *stream, const float *cls_logits, co
         hipError_t e = hipMemsetAsync(ws.maxc, 0, align256(sizeof(float) * (size_t)B) + sizeof(int) * (size_t)B, st);
         if (e != hipSuccess) return semidetr::fail((int)e, "pseudo_nms memset: %s", hipGetErrorString(e));
     }
-    hipLaunchKernelGGL(nms_prepare_kernel, dim3((Q + kPrepQueries - 1) / kPrepQueries, B), dim3(256), 0, st, cls_logits, bbox_pred, img_hw, Q, C,
-                       score_thr, ws);
+    hipLaunchKernelGGL(nms_prepare_kernel<HW>, dim3((Q + kPrepQueries - 1) / kPrepQueries, B), dim3(256), 0, st, cls_logits,
+                       bbox_pred, hw, Q, C, score_thr, ws);
     if (int rc = semidetr::launch_status("nms_prepare_kernel")) return rc;
     // one wavefront per problem for short candidate lists, four for the DINO query counts (the kept-list scan is
     // quadratic in the list length)
@@ -386,6 +408,42 @@ extern "C" int semidetr_pseudo_nms_f32(void *stream, const float *cls_logits, co
     return semidetr::launch_status("nms_topk_kernel");
 }
 
+}  // namespace
+
+extern "C" int semidetr_pseudo_nms_f32(void *stream, const float *cls_logits, const float *bbox_pred,
+                                       const float *img_hw, int batch, int num_query, int num_classes,
+                                       float score_thr, float iou_thr, int max_per_img, void *workspace,
+                                       size_t workspace_bytes_, float *out_dets, int64_t *out_labels,
+                                       int32_t *out_count)
+{
+    return pseudo_nms(semidetr::as_stream(stream), cls_logits, bbox_pred, semidetr::DeviceHw{img_hw}, img_hw != nullptr, batch,
+                      num_query, num_classes, score_thr, iou_thr, max_per_img, workspace, workspace_bytes_, out_dets, out_labels,
+                      out_count);
+}
+
+extern "C" int semidetr_teacher_pseudo_labels_f32(void *stream, const float *cls_logits, const float *bbox_pred,
+                                                  const semidetr_image_sizes *img_hw, int num_query, int num_classes,
+                                                  float score_thr, float iou_thr, int max_per_img, void *workspace,
+                                                  size_t workspace_bytes_, float *out_dets, int64_t *out_det_labels,
+                                                  float *out_boxes, int64_t *out_labels, float *out_scores, int32_t *counts,
+                                                  float *out_thr)
+{
+    SEMIDETR_REQUIRE(img_hw, SEMIDETR_E_BADARG, "teacher_pseudo_labels: null img_hw");
+    const int B = img_hw->num_images;
+    SEMIDETR_REQUIRE(B >= 1 && B <= SEMIDETR_IMAGE_TABLE, SEMIDETR_E_BADARG, "teacher_pseudo_labels: %d images (1 .. %d fit the table)",
+                     B, SEMIDETR_IMAGE_TABLE);
+    SEMIDETR_REQUIRE(counts && out_thr && out_boxes && out_labels && out_scores && out_dets && out_det_labels, SEMIDETR_E_BADARG,
+                     "teacher_pseudo_labels: null pointer argument");
+    SEMIDETR_REQUIRE(max_per_img >= 1 && (int64_t)B * max_per_img < INT32_MAX, SEMIDETR_E_BADARG,
+                     "teacher_pseudo_labels: bad max_per_img (%d)", max_per_img);
+    hipStream_t st = semidetr::as_stream(stream);
+    if (int rc = pseudo_nms(st, cls_logits, bbox_pred, semidetr::ValueHw{*img_hw}, true, B, num_query, num_classes, score_thr,
+                            iou_thr, max_per_img, workspace, workspace_bytes_, out_dets, out_det_labels, counts))
+        return rc;
+    return semidetr::launch_pseudo_filter_padded(st, out_dets, out_det_labels, max_per_img, counts, B, out_boxes, out_labels,
+                                                 out_scores, counts + B, out_thr);
+}
+
 extern "C" int semidetr_transform_bboxes_f32(void *stream, const float *boxes, int box_stride,
                                              const int32_t *box_offsets, const int32_t *box_counts,
                                              int num_images, int max_boxes_per_image, const float *matrices,
@@ -396,8 +454,30 @@ extern "C" int semidetr_transform_bboxes_f32(void *stream, const float *boxes, i
     SEMIDETR_REQUIRE(boxes && box_offsets && matrices && out_hw && out_boxes, SEMIDETR_E_BADARG,
                      "transform_bboxes: null pointer argument");
     SEMIDETR_REQUIRE(box_stride >= 4, SEMIDETR_E_BADARG, "transform_bboxes: box_stride must be >= 4 (got %d)", box_stride);
-    hipLaunchKernelGGL(transform_bboxes_kernel, dim3((max_boxes_per_image + 255) / 256, num_images), dim3(256), 0,
-                       semidetr::as_stream(stream), boxes, box_stride, box_offsets, box_counts, matrices, out_hw,
+    hipLaunchKernelGGL(transform_bboxes_kernel<BatchBoxes>, dim3((max_boxes_per_image + 255) / 256, num_images), dim3(256), 0,
+                       semidetr::as_stream(stream), BatchBoxes{boxes, box_stride, box_offsets, box_counts, matrices, out_hw},
                        out_boxes);
+    return semidetr::launch_status("transform_bboxes_kernel");
+}
+
+extern "C" int semidetr_transform_bboxes_table_f32(void *stream, const semidetr_box_table *table, float *out_boxes)
+{
+    SEMIDETR_REQUIRE(table, SEMIDETR_E_BADARG, "transform_bboxes_table: null table");
+    const int B = table->num_images;
+    SEMIDETR_REQUIRE(B >= 1 && B <= SEMIDETR_IMAGE_TABLE, SEMIDETR_E_BADARG,
+                     "transform_bboxes_table: %d images (1 .. %d fit the table)", B, SEMIDETR_IMAGE_TABLE);
+    int max_boxes = 0;
+    for (int b = 0; b < B; ++b) {
+        const int n = table->count[b];
+        SEMIDETR_REQUIRE(n >= 0 && table->out_offset[b] >= 0, SEMIDETR_E_BADARG, "transform_bboxes_table: image %d: count %d, row %d",
+                         b, n, table->out_offset[b]);
+        SEMIDETR_REQUIRE(n == 0 || (table->boxes[b] && table->matrix[b] && table->box_stride[b] >= 4), SEMIDETR_E_BADARG,
+                         "transform_bboxes_table: image %d: null boxes / matrix or a row stride below 4", b);
+        max_boxes = n > max_boxes ? n : max_boxes;
+    }
+    if (max_boxes == 0) return SEMIDETR_OK;
+    SEMIDETR_REQUIRE(out_boxes, SEMIDETR_E_BADARG, "transform_bboxes_table: null out_boxes");
+    hipLaunchKernelGGL(transform_bboxes_kernel<TableBoxes>, dim3((max_boxes + 255) / 256, B), dim3(256), 0,
+                       semidetr::as_stream(stream), TableBoxes{*table}, out_boxes);
     return semidetr::launch_status("transform_bboxes_kernel");
 }

@@ -9,7 +9,9 @@ Mirrors, name for name and argument for argument:
   * ``O2MAssigner`` / ``O2MAssignResult``  detr_od/core/bbox/assigners/o2m_assigner.py:17-170, o2m_assign_result.py:6-52
     (the warm-up stage's one-to-many assigner, ``csrc/o2m.hip``)
 and adds ``HungarianAssigner.assign_batch`` -- all (decoder layer x image) problems of a ``loss()`` call
-in two launches and at most one host sync (only to raise scipy's ``ValueError`` on NaN / infeasible input).
+in two launches and at most one host sync (only to raise scipy's ``ValueError`` on NaN / infeasible input); where every
+ground-truth tensor can be read in place, the two launches are one C-ABI call without staging copies
+(``hungarian_assign_batch``, ``csrc/hungarian_assign.hip``).
 When mmdet/mmcv are importable the classes are registered under the reference's names (see ``registry.py``).
 """
 import ctypes
@@ -103,6 +105,85 @@ def lsap_batch(cost_flat, offs_dev, offs, Q, gt_labels=None, want_pairs=True, wa
     _lib.call("semidetr_lsap_solve", dev, cost_flat, offs_dev, gt_labels, B, Q, total, max_gt, rows, cols, gt_inds, labels,
               status, ws)
     return dict(rows=rows, cols=cols, pair_offsets=pair_offs, gt_inds=gt_inds, labels=labels, status=status)
+
+
+# Take semidetr_hungarian_assign_f32 (one call, the ground truths read where they are) when the inputs allow it; False forces the
+# three calls on the concatenated ground truths (tests compare the two).
+NATIVE_CHAIN = True
+
+
+def pack_match_table(box_ptrs, label_ptrs, counts, img_wh):
+    """The by-value ground-truth table of ``semidetr_hungarian_assign_f32`` from host lists (one entry per problem: device
+    pointers, count, (img_w, img_h)); returns (table, offsets host list)."""
+    B = len(counts)
+    if not 1 <= B <= _lib.MATCH_TABLE or not len(box_ptrs) == len(label_ptrs) == len(img_wh) == B:
+        raise ValueError(f"pack_match_table: {B} problems (1 .. {_lib.MATCH_TABLE} fit the table, one entry of each list per problem)")
+    offs = [0]
+    for c in counts:
+        offs.append(offs[-1] + c)
+    t = _lib.MatchTable()
+    t.num_problems = B
+    t.count[:B] = counts
+    t.offsets[:B + 1] = offs
+    t.boxes[:B] = box_ptrs
+    t.labels[:B] = label_ptrs
+    for b, (w, h) in enumerate(img_wh):
+        t.img_wh[b][0], t.img_wh[b][1] = w, h
+    return t, offs
+
+
+def _table_inputs_ok(gt_bboxes_list, gt_labels_list, dev):
+    """The fall-back conditions of the one-call path: it reads every ground-truth tensor in place, so each has to be what the
+    kernels read -- (G, 4) fp32 contiguous and (G,) int64 contiguous on ``dev``; anything else goes through the casts of the
+    three-call path."""
+    B = len(gt_bboxes_list)
+    if not NATIVE_CHAIN or not 1 <= B <= _lib.MATCH_TABLE or len(gt_labels_list) != B:
+        return False
+    for g, l in zip(gt_bboxes_list, gt_labels_list):
+        if (g.dtype != torch.float32 or l.dtype != torch.int64 or g.device != dev or l.device != dev or g.dim() != 2
+                or g.size(1) != 4 or l.dim() != 1 or l.size(0) != g.size(0) or not g.is_contiguous() or not l.is_contiguous()
+                or g.data_ptr() % 16 or l.data_ptr() % 8):
+            return False
+    return True
+
+
+def hungarian_assign_batch(bbox_pred, cls_pred, gt_bboxes_list, gt_labels_list, img_metas, params, want_pairs=False,
+                           num_classes=None):
+    """Cost, assignment and (``num_classes`` given) training targets of all problems in ONE C-ABI call and no staging copy: the
+    ground-truth tensors are read in place through a table in the kernel arguments (the tensors only have to live until the call
+    returns and the stream has run).  Returns (cost_flat, offs host list, what ``lsap_batch`` returns, targets dict or None), the
+    same tensors the three calls give.  The caller has checked ``_table_inputs_ok``."""
+    _require_cuda(bbox_pred, cls_pred)
+    B, Q, C = cls_pred.shape
+    dev = bbox_pred.device
+    bbox_pred = bbox_pred.detach().to(torch.float32).contiguous()
+    cls_pred = cls_pred.detach().to(torch.float32).contiguous()
+    counts = [g.size(0) for g in gt_bboxes_list]
+    table, offs = pack_match_table([g.data_ptr() for g in gt_bboxes_list], [l.data_ptr() for l in gt_labels_list], counts,
+                                   [(m["img_shape"][1], m["img_shape"][0]) for m in img_metas])
+    total, max_gt = offs[-1], max(counts)
+    pair_offs = [0]
+    for c in counts:
+        pair_offs.append(pair_offs[-1] + min(Q, c))
+    cost = torch.empty(Q * total, dtype=torch.float32, device=dev)
+    rows = torch.empty(pair_offs[-1], dtype=torch.int64, device=dev) if want_pairs else None
+    cols = torch.empty(pair_offs[-1], dtype=torch.int64, device=dev) if want_pairs else None
+    gt_inds = torch.empty((B, Q), dtype=torch.int64, device=dev)
+    labels = torch.empty((B, Q), dtype=torch.int64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    ws_bytes = _lib.lib().semidetr_lsap_workspace_bytes(B, Q, max_gt)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    tg = None
+    if num_classes is not None:
+        tg = dict(labels=torch.empty((B, Q), dtype=torch.int64, device=dev),
+                  label_weights=torch.empty((B, Q), dtype=torch.float32, device=dev),
+                  bbox_targets=torch.empty((B, Q, 4), dtype=torch.float32, device=dev),
+                  bbox_weights=torch.empty((B, Q, 4), dtype=torch.float32, device=dev),
+                  num_pos=torch.empty(B, dtype=torch.int32, device=dev))
+    _lib.call("semidetr_hungarian_assign_f32", dev, bbox_pred, cls_pred, ctypes.byref(table), Q, C, ctypes.byref(params), cost,
+              rows, cols, gt_inds, labels, status, ws, int(num_classes or 0), *(tg.values() if tg else (None,) * 5))
+    res = dict(rows=rows, cols=cols, pair_offsets=pair_offs, gt_inds=gt_inds, labels=labels, status=status)
+    return cost, offs, res, tg
 
 
 def raise_on_status(status):
@@ -233,12 +314,16 @@ class HungarianAssigner:
         B, Q = bbox_preds.shape[0], bbox_preds.shape[1]
         dev = bbox_preds.device
         counts = [int(g.size(0)) for g in gt_bboxes_list]
-        gt_b = torch.cat([g.reshape(-1, 4) for g in gt_bboxes_list]) if B else bbox_preds.new_zeros((0, 4))
-        gt_l = torch.cat([g.reshape(-1).long() for g in gt_labels_list]) if B else bbox_preds.new_zeros(0).long()
-        wh = _lib.small_to_device([[m["img_shape"][1], m["img_shape"][0]] for m in img_metas], torch.float32, dev)
-        cost, offs_dev, offs = match_cost_batch(bbox_preds, cls_preds, gt_b, gt_l, counts, wh,
-                                                self._cost_params())
-        res = lsap_batch(cost, offs_dev, offs, Q, gt_labels=gt_l, want_pairs=return_cost)
+        if len(img_metas) == B and _table_inputs_ok(gt_bboxes_list, gt_labels_list, dev):
+            cost, offs, res, _ = hungarian_assign_batch(bbox_preds, cls_preds, gt_bboxes_list, gt_labels_list, img_metas,
+                                                        self._cost_params(), want_pairs=return_cost)
+        else:
+            gt_b = torch.cat([g.reshape(-1, 4) for g in gt_bboxes_list]) if B else bbox_preds.new_zeros((0, 4))
+            gt_l = torch.cat([g.reshape(-1).long() for g in gt_labels_list]) if B else bbox_preds.new_zeros(0).long()
+            wh = _lib.small_to_device([[m["img_shape"][1], m["img_shape"][0]] for m in img_metas], torch.float32, dev)
+            cost, offs_dev, offs = match_cost_batch(bbox_preds, cls_preds, gt_b, gt_l, counts, wh,
+                                                    self._cost_params())
+            res = lsap_batch(cost, offs_dev, offs, Q, gt_labels=gt_l, want_pairs=return_cost)
         if check:
             raise_on_status(res["status"])
         out = []
@@ -261,6 +346,12 @@ class HungarianAssigner:
         ``(gt_inds[b] > 0).nonzero()`` / ``(gt_inds[b] == 0).nonzero()`` when a caller wants index lists."""
         B, Q = bbox_preds.shape[0], bbox_preds.shape[1]
         dev = bbox_preds.device
+        if len(img_metas) == B and _table_inputs_ok(gt_bboxes_list, gt_labels_list, dev):
+            _, _, res, tg = hungarian_assign_batch(bbox_preds, cls_preds, gt_bboxes_list, gt_labels_list, img_metas,
+                                                   self._cost_params(), num_classes=int(num_classes))
+            if check:
+                raise_on_status(res["status"])
+            return dict(tg, gt_inds=res["gt_inds"], status=res["status"])
         counts = [int(g.size(0)) for g in gt_bboxes_list]
         gt_b = torch.cat([g.reshape(-1, 4) for g in gt_bboxes_list]).to(torch.float32).contiguous()
         gt_l = torch.cat([g.reshape(-1).long() for g in gt_labels_list]).contiguous()
