@@ -1,4 +1,5 @@
-// Shared host-side helpers for libsemidetr_hip.so (error reporting, launch checks, the grant of large dynamic LDS).
+// Shared host-side helpers for libsemidetr_hip.so (error reporting, launch checks, the grant of large dynamic LDS, the split
+// rule of the MSDA forwards).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -32,6 +33,19 @@ template <typename K>
 inline int allow_big_lds(K *kernel, size_t bytes, const char *what)
 {
     return allow_big_lds(reinterpret_cast<const void *>(kernel), bytes, what);
+}
+
+// SPLIT of the D == 32 MSDA forwards (fp32: msda_dispatch.h, 16-bit value maps: msda_h16.hip) = the number of 8-lane groups that
+// share one query row: with enough 32-row workgroups to fill 256 CUs several times over no split; otherwise the samples of a
+// row are spread over more lanes, so that small problems (decoder, 300-900 queries) still fill the chip.  forced: 1 / 2 / 4
+// takes that split (the experiments dispatch), anything else the rule.
+inline int pick_split(int forced, int N, int Lq, int M)
+{
+    if (forced == 1 || forced == 2 || forced == 4) return forced;
+    const int64_t wg32 = (int64_t)N * M * ((Lq + 31) / 32);
+    if (wg32 >= 2048) return 1;
+    if (wg32 >= 1024) return 2;
+    return 4;
 }
 
 // the smallest power of two >= v, at least 2 (a bitonic network needs a pair)

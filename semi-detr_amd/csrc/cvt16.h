@@ -1,4 +1,5 @@
-// The two 16-bit storage types of the mixed-precision kernels (msda_h16.hip, add_norm.hip): exact up-cast, one
+// The two 16-bit storage types of the mixed-precision kernels (msda_h16.hip -- the value rows and, in RawIO16, the raw offsets /
+// logits --, add_norm.hip, self_attn.hip, group_norm_tokens.hip, ref_points.hip): exact up-cast, one
 // round-to-nearest-even down-cast (fp16 overflows to inf, as the conversion does), and the pack / unpack of four neighbouring
 // elements = two dwords.  T16 = __half | __hip_bfloat16.  Included INSIDE the namespace of the file that uses it, after
 // <hip/hip_runtime.h>, <hip/hip_fp16.h> and <hip/hip_bf16.h>.

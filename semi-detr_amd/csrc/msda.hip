@@ -161,6 +161,7 @@ __global__ __launch_bounds__(256) void msda_bwd_generic(
     }
 }
 
+#include "msda_lanes.h"  // DPP lane reductions + the workgroup -> tile mapping, shared with msda_h16.hip
 #include "msda_fast.h"   // IO policies + the D == 32 fp32 kernels
 #if SEMIDETR_EXPERIMENTS
 #include "msda_fast_experiments.h"   // windowed scatter, resident-level forward, 512-thread merged / cooperative-fill backward

@@ -29,18 +29,8 @@ bool heads_ok(int M) { return (int64_t)M * kD * 4 <= 4096; }
 // the fast-path kernels address one image's value slice with 32-bit BYTE offsets (buffer instructions)
 bool slice_ok(int S, int M) { return (int64_t)S * M * kD * 4 < (int64_t)0xFFFFF000u; }
 
-int pick_split(int forced, int N, int Lq, int M)
-{
-    if (forced == 1 || forced == 2 || forced == 4) return forced;
-    // enough 32-row workgroups to fill 256 CUs several times over -> no split; otherwise spread the
-    // samples of a row over more lanes so small problems (decoder, 300-900 queries) still fill the chip.
-    const int64_t wg32 = (int64_t)N * M * ((Lq + 31) / 32);
-    if (wg32 >= 2048) return 1;
-    if (wg32 >= 1024) return 2;
-    return 4;
-}
-
-using semidetr::allow_big_lds;      // (kernels of one signature share the pointer TYPE; the grant is keyed on the pointer VALUE)
+using semidetr::pick_split;         // (common.h: the one rule of the fp32 and the 16-bit forward)
+using semidetr::allow_big_lds;     // (kernels of one signature share the pointer TYPE; the grant is keyed on the pointer VALUE)
 
 // ---- grid-size hints.  The level table lives in device memory, so a launch that has no host copy of it cannot know how many patches /
 //      regions its pyramid has.  The kernels enumerate their units on the device: a workgroup takes units slot, slot + bound, slot + 2 x

@@ -1,7 +1,8 @@
 // Fast-path device code of the multi-scale deformable attention for gfx950 (fp32, 32 channels per head):
 // IO policies (reference op contract / fused MSDeformAttn prologue), forward, plain backward, and the
 // gather + owner-computes scatter pair used for encoder self-attention.  Included by msda.hip only (inside
-// its anonymous namespace); see msda_geom.h for the shared sample geometry and msda_dispatch.h for the host-side dispatch.
+// its anonymous namespace, after msda_geom.h -- the shared sample geometry -- and msda_lanes.h -- the shared lane reductions and
+// the workgroup -> tile mapping); see msda_dispatch.h for the host-side dispatch.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
@@ -157,8 +158,6 @@ struct LocAttnIO {
 #endif
 };
 
-__device__ __forceinline__ float rawio_group_sum(float x, int LP);      // = lp_group_sum, defined below (needs dpp_mov)
-
 struct RawIO {
     const float *ref, *off, *logit;      // (N,Lq,L,ref_dim), (N,Lq,M,L,P,2), (N,Lq,M,L*P)
     float *goff, *glogit;
@@ -281,7 +280,7 @@ struct RawIO {
     {
         float dot = res.w * res.x;               // softmax backward: a_k * (g_k - sum_j a_j g_j)
         if ((LP & (LP - 1)) == 0 && LP <= 64) {
-            dot = rawio_group_sum(dot, LP);
+            dot = lp_group_sum(dot, LP);
         } else {                                 // generic LP: every thread re-reads the row (rare)
             dot = 0.f;
             for (int j = 0; j < LP; ++j) dot += row_res[j].w * row_res[j].x;
@@ -387,12 +386,6 @@ __device__ unsigned long long g_dest_dbg[16];
 #define SEMIDETR_DBG_ADD(SLOT_, V_) ((void)0)
 #endif
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x)
-{
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
 // sum over the 8 lanes of a group: quad xor1, quad xor2, then mirror inside the half-row (i <-> 7-i).
 __device__ __forceinline__ float group8_sum(float x)
 {
@@ -426,31 +419,8 @@ __device__ __forceinline__ void group8_sum3(float &a, float &b, float &c)
 
 // Softmax over the L*P logits of one (n, q, m) row (ms_deform_attn.py:101), evaluated cooperatively by the LP
 // consecutive threads that own the row's samples: one expf per sample, max / sum by xor-shuffles when LP is a
-// power of two <= 64 (the DINO case LP = 16 is one DPP row); any other LP falls back to a per-thread loop.
-__device__ __forceinline__ bool lp_shuffles(int LP) { return (LP & (LP - 1)) == 0 && LP <= 64; }
-// sum / max over a lane-aligned group of LP threads (LP a power of two <= 64); every lane of the group gets the result
-__device__ __forceinline__ float lp_group_sum(float x, int LP)
-{
-    if (LP >= 2) x += dpp_mov<0xB1>(x);      // quad_perm [1,0,3,2]
-    if (LP >= 4) x += dpp_mov<0x4E>(x);      // quad_perm [2,3,0,1]
-    if (LP >= 8) x += dpp_mov<0x141>(x);     // row_half_mirror
-    if (LP >= 16) x += dpp_mov<0x140>(x);    // row_mirror
-    if (LP >= 32) x += __shfl_xor(x, 16, 64);
-    if (LP >= 64) x += __shfl_xor(x, 32, 64);
-    return x;
-}
-__device__ __forceinline__ float rawio_group_sum(float x, int LP) { return lp_group_sum(x, LP); }
-__device__ __forceinline__ float lp_group_max(float x, int LP)
-{
-    if (LP >= 2) x = fmaxf(x, dpp_mov<0xB1>(x));
-    if (LP >= 4) x = fmaxf(x, dpp_mov<0x4E>(x));
-    if (LP >= 8) x = fmaxf(x, dpp_mov<0x141>(x));
-    if (LP >= 16) x = fmaxf(x, dpp_mov<0x140>(x));
-    if (LP >= 32) x = fmaxf(x, __shfl_xor(x, 16, 64));
-    if (LP >= 64) x = fmaxf(x, __shfl_xor(x, 32, 64));
-    return x;
-}
-
+// power of two <= 64 (the DINO case LP = 16 is one DPP row; lp_shuffles, lp_group_max / lp_group_sum: msda_lanes.h); any other
+// LP falls back to a per-thread loop.
 template <typename IO, typename R>
 __device__ __forceinline__ float row_softmax(const IO &io, R row, int LP, int k, float raw)
 {
@@ -536,40 +506,7 @@ __device__ __forceinline__ void softmax_rows_to_lds(const IO &io, int tid, int R
     }
 }
 
-// Workgroup -> (n, query tile, m).  Consecutive workgroups take consecutive heads, and the head of a given slot is
-// rotated every kHeadRun tiles.  Why: rows of one head are M*128 bytes apart, so with M == 8 all addresses one head
-// touches share bits [9:7]; workgroups go round robin to the 8 XCDs, so "blockIdx % 8 == head" pins each XCD to
-// ONE such address class for the whole launch.  Measured at the encoder shape, bs 4 (rocprofv3 PMC,
-// profiles/r01_msda_fwd_enc_mapping_pmc.txt): with the rotation the L1 traffic and L1 miss traffic are identical
-// (91 M accesses, 15.4 M L1->L2 requests), L2 misses go UP 3.5 M -> 4.9 M, yet forward 286 -> 248 us, gather
-// 341 -> 320 us, decoder forward 24.7 -> 20.8 us.  Run lengths 2..512 are equivalent in time (242-260 us; longer
-// runs re-fetch fewer halo rows across XCDs: HBM reads 540 MB at 64, 418 MB at 256, 356 MB without rotation -- but
-// the bench step was 1.5 % slower with 256 or a launch-size dependent length), 1 (adjacent tiles on different XCDs)
-// gives 278, 2048 gives 268, >= 8192 is no rotation in practice.  Since a run of 512 tiles (one head per XCD at any
-// instant, ~7 different heads per XCD over the launch) is as good as 64, what matters is that no XCD stays married
-// to one address class: the classes are not equally fast from every XCD once the accesses leave the L2
-// (tools/xcd_class_probe.hip: up to 1.5x between (XCD, class) pairs), every XCD has the same amount of work, and the
-// launch ends with the slowest one.  Giving every XCD all 8 heads of a contiguous eighth of the
-// tiles was as slow as no rotation (not understood); a head-major copy of the value map (N,M,S,D) brought nothing
-// on top.  Speed only -- any bijection is correct.
-constexpr int kHeadRun = 64;
-struct Tile {
-    int n, q0, m;
-};
-__device__ __forceinline__ Tile tile_of(int b, int M, int tiles_per_image, int rows_per_block);
-__device__ __forceinline__ Tile tile_of_block(int M, int tiles_per_image, int rows_per_block)
-{
-    return tile_of((int)blockIdx.x, M, tiles_per_image, rows_per_block);
-}
-__device__ __forceinline__ Tile tile_of(int b, int M, int tiles_per_image, int rows_per_block)
-{
-    Tile t;
-    const int r = b / M;
-    t.m = (b % M + r / kHeadRun) % M;
-    t.q0 = (r % tiles_per_image) * rows_per_block;
-    t.n = r / tiles_per_image;
-    return t;
-}
+// (Workgroup -> (n, query tile, m): Tile / tile_of / tile_of_block and kHeadRun with its measurements are msda_lanes.h's)
 
 // Encoder self-attention (num_query == spatial_size: query i IS pixel i of the multi-scale map): instead of
 // 32 consecutive pixels (a 32 x 1 strip) a workgroup can take a PH x PW patch of one level -- its samples
@@ -974,19 +911,6 @@ __global__ __launch_bounds__(kWsThreads) void msda_fwd_d32_ws(
     }
 }
 #endif      // SEMIDETR_EXPERIMENTS
-
-// Sum over the 32 lanes of each wavefront half (lane = channel).  After the five steps lanes 16..31 of
-// each half hold the half's total; the writer is lane 16 / 48.
-__device__ __forceinline__ float half32_sum(float x)
-{
-    x += dpp_mov<0xB1>(x);    // quad_perm [1,0,3,2]
-    x += dpp_mov<0x4E>(x);    // quad_perm [2,3,0,1]
-    x += dpp_mov<0x141>(x);   // row_half_mirror
-    x += dpp_mov<0x140>(x);   // row_mirror  -> every lane of a 16-lane row holds the row total
-    // row_bcast:15 into rows 1 and 3 (row_mask 0xA): lane 15 of the previous row is added to every lane
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x142, 0xA, 0xF, true));
-    return x;
-}
 
 // Backward, fp32 / D == 32.  One value row (128 B) per 32 lanes, lane = channel: every global_atomic_add_f32
 // wave-instruction updates two COMPLETE cache lines.  Measured on MI355X (tools/atomic_probe.hip): L2 fp32

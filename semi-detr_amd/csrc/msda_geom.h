@@ -2,7 +2,8 @@
 // value maps): the pixel mapping with its individually rounded multiply / subtract, the corner records in element and in byte
 // form, and the bounds-checked buffer loads whose out-of-range result IS the op's zero padding.  Included INSIDE the including
 // file's (anonymous) namespace, after <hip/hip_runtime.h>; both files sample with this one copy, so a 16-bit value map selects
-// exactly the cells the fp32 op selects.
+// exactly the cells the fp32 op selects.  (msda_lanes.h is the sibling header for what the two files' fast kernels share beyond
+// the geometry: the DPP lane reductions and the workgroup -> tile mapping.)
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
@@ -79,7 +80,7 @@ __device__ __forceinline__ bool sample_setup_oob(float x, float y, int H, int W,
 
 // ---------------------------------------------------------------------------------------------
 // location arithmetic of the fused MSDeformAttn prologue (ms_deform_attn.py:102-108), shared by the fp32 kernels' RawIO
-// (msda_fast.h) and the 16-bit kernels (msda_h16.hip): loc = ref + off * scale, per coordinate
+// (msda_fast.h) and the 16-bit kernels' RawIO16 (msda_h16.hip): loc = ref + off * scale, per coordinate
 // ---------------------------------------------------------------------------------------------
 // 1 / x as ONE v_rcp_f32 (1 ulp).  __frcp_rn is the correctly rounded reciprocal -- on gfx950 the full IEEE division
 // sequence (v_div_scale / v_rcp / 4 fma / v_div_fmas / v_div_fixup), ten instructions where the fused prologue wants one.

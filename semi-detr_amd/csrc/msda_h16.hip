@@ -12,31 +12,37 @@
 // weights are never narrowed, the pixel mapping is msda_geom.h's (the same code msda.hip samples with), and corners outside
 // a level are never loaded (bounds-checked buffer loads / exec-masked loads).
 //
-// Kernels (T16 = __half | __hip_bfloat16):
-//  * msda_fwd_h16<T16, SPLIT>       32 channels per head, <= 32 heads, any query set.  The shape of msda_fwd_d32 (msda_fast.h):
+// Kernels (T16 = __half | __hip_bfloat16).  As in msda_fast.h, each fast kernel is ONE template over an IO policy that says where
+// a sample's (x, y, attention) and its corner mask come from and where the backward puts the two small gradients:
+//   LocAttnIO16   the reference op contract: fp32 locations and softmaxed weights in, fp32 grad_loc / grad_attn out
+//                 (semidetr_msda_{forward,backward}_h16; reported as msda_fwd_h16<SPLIT / msda_bwd_h16);
+//   RawIO16<PT>   the MSDeformAttn prologue / epilogue inside (semidetr_msda_fused_{forward,backward}_h16; reported as
+//                 msda_fwd_h16_fused<SPLIT / msda_bwd_h16_fused): fp32 reference points, the RAW offsets and logits (PT = float |
+//                 T16) and the padding mask bytes; softmax over L * P and ref + off * scale (msda_geom.h fused_loc_xy, the fp32
+//                 kernels' code) in fp32; the write-back applies the softmax backward and the offset scale and rounds a 16-bit
+//                 PT once.
+//  * msda_fwd_h16<T16, IO, SPLIT>   32 channels per head, <= 32 heads, any query set.  The shape of msda_fwd_d32 (msda_fast.h):
 //                                   phase 1 turns the tile's samples into LDS records {4 corner byte offsets, 4 weights};
 //                                   phase 2 covers one 64-byte value row with 8 lanes x ONE 8-byte buffer load of 4 channels,
 //                                   so lane -> channel map and fp32 accumulation order are msda_fwd_d32's (8 lanes x float4).
-//  * msda_bwd_h16<T16>              same shapes.  The shape of msda_bwd_d32: 32 lanes per value row (lane = channel), so every
+//  * msda_bwd_h16<T16, IO>          same shapes.  The shape of msda_bwd_d32: 32 lanes per value row (lane = channel), so every
 //                                   global_atomic_add_f32 wave-instruction updates two complete 128-byte workspace rows;
 //                                   channel sums for grad_attn / grad_loc by DPP inside the half-wave, staged in LDS.
 //  * msda_h16_convert<T16>          fp32 workspace -> 16-bit grad_value, 8 elements (one 16-byte store) per thread.
-//  * msda_{fwd,bwd}_h16_generic<T16> any D, any head count, any alignment: one wavefront per (n, q, m) row, lane per channel.
-//  * msda_fwd_h16_fused<T16, PT, SPLIT>, msda_bwd_h16_fused<T16, PT>: the two fast kernels with the MSDeformAttn prologue / epilogue
-//                                   inside (semidetr_msda_fused_{forward,backward}_h16): the sample records come from the fp32
-//                                   reference points, the RAW offsets and logits (PT = float | T16) and the padding mask bytes;
-//                                   softmax over L * P and ref + off * scale (msda_geom.h fused_loc_xy, the fp32 kernels' code) in
-//                                   fp32; the backward's write-back applies the softmax backward and the offset scale and rounds a
-//                                   16-bit PT once.  The gather / row phases are the SAME device functions as the unfused kernels'.
+//  * msda_{fwd,bwd}_h16_generic<T16> any D, any head count, any alignment: one wavefront per (n, q, m) row, lane per channel
+//                                   (reference contract only: there is no generic fused kernel).
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
+
+#include <type_traits>
 
 #include "common.h"
 
 namespace semidetr_h16 {
 
 #include "msda_geom.h"
+#include "msda_lanes.h"              // dpp_mov, half32_sum, lp_group_max / lp_group_sum, Tile / tile_of_block: the fp32 kernels' own
 
 constexpr int kD = 32;              // channels per head of the fast path
 constexpr int kMaxLevels = 32;
@@ -46,22 +52,6 @@ thread_local const char *g_last_kernels = "";
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
-// Sum over the 32 lanes of each wavefront half (the reduction of msda_bwd_d32, msda_fast.h half32_sum): lanes 16..31 of each
-// half hold the half's total afterwards; the writer is lane 16 / 48.
-__device__ __forceinline__ float half32_sum(float x)
-{
-    x += dpp_mov<0xB1>(x);    // quad_perm [1,0,3,2]
-    x += dpp_mov<0x4E>(x);    // quad_perm [2,3,0,1]
-    x += dpp_mov<0x141>(x);   // row_half_mirror
-    x += dpp_mov<0x140>(x);   // row_mirror
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x142, 0xA, 0xF, true));   // row_bcast:15
-    return x;
-}
 __device__ __forceinline__ float wave_sum(float v)
 {
 #pragma unroll
@@ -69,24 +59,225 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
-// Workgroup -> (image, first query row, head): consecutive workgroups take consecutive heads and the head of a slot is rotated
-// every 64 tiles, so that no XCD stays with one address class of the value map (measured on the fp32 kernels: msda_fast.h,
-// tile_of).  Speed only -- any bijection is correct.
-struct Tile {
-    int n, q0, m;
+// ---------------------------------------------------------------------------------------------------------------------
+// IO policies of the fast kernels: what LocAttnIO / RawIO (msda_fast.h) are to the fp32 kernels, under the same names where the
+// meaning is the same -- kSoftmax, record(...) (the record-building call), store(...).  Not merged with the fp32 structs: these
+// store plainly (nothing streams), test the padding mask byte by byte (no summarised extents) and need no 32-bit image view.
+//   begin_tile(...)  once per workgroup, by all threads: what the policy sets up for the tile (TileState)
+//   record(...)      one sample of the tile -> its corner byte offsets (kOob: never loaded, no gradient), the bilinear fractions
+//                    and the attention weight `a`; returns whether the sample is on the map
+//   store(...)       the backward's write-back of one sample: res = {d/d a_k, d/d loc.x, d/d loc.y, a_k}, row_res = the L * P
+//                    results of the same (n, q, m) row
+//   softmax_lds      (host) LDS bytes beyond the records that `rows` query rows need
+// ---------------------------------------------------------------------------------------------------------------------
+struct LocAttnIO16 {
+    const float *loc, *attn;        // (N, Lq, M, L, P, 2), (N, Lq, M, L * P): fp32, attn already holds probabilities
+    float *gloc, *gattn;            // their gradients, fp32 and unrounded (backward; null in the forward)
+    static constexpr bool kSoftmax = false;
+    static constexpr const char *kFwd[3] = {"msda_fwd_h16<1", "msda_fwd_h16<2", "msda_fwd_h16<4"};      // by log2(SPLIT)
+    static constexpr const char *kBwd = "msda_bwd_h16+msda_h16_convert";
+    static size_t softmax_lds(int rows, int LP) { (void)rows; (void)LP; return 0; }
+    struct TileState {};
+    __device__ __forceinline__ TileState begin_tile(const Tile t, int rows, int M, int L, int P, int Lq, float *sm) const
+    {
+        (void)t; (void)rows; (void)M; (void)L; (void)P; (void)Lq; (void)sm;
+        return TileState{};
+    }
+    // `live`: the thread has a sample slot and that slot's query row exists; l = k / P, the sample's level
+    __device__ __forceinline__ bool record(const TileState &ts, const int64_t *__restrict__ shapes, const int64_t *__restrict__ starts,
+                                           bool in, bool live, int n, int q, int64_t row, int r, int k, int l, int S, int L, int P,
+                                           unsigned row_bytes, unsigned (&off)[4], float &lw, float &lh, float &a) const
+    {
+        (void)ts; (void)in; (void)n; (void)q; (void)r; (void)S;
+        off[0] = off[1] = off[2] = off[3] = kOob;      // out of range -> the hardware returns zeros
+        lw = lh = a = 0.f;
+        if (!live) return false;
+        const int LP = L * P;
+        const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1], st = (int)starts[l];
+        const float2 xy = *reinterpret_cast<const float2 *>(loc + (row * LP + k) * 2);
+        a = attn[row * LP + k];
+        return sample_setup_oob(xy.x, xy.y, H, W, st, row_bytes, off, lw, lh);
+    }
+    // grad_attn_weight / grad_sampling_loc as they are
+    __device__ __forceinline__ void store(const TileState &ts, int64_t row, int q, int k, int l, int L, int P, int H, int W,
+                                          const float4 res, const float4 *row_res) const
+    {
+        (void)ts; (void)q; (void)l; (void)H; (void)W; (void)row_res;
+        const int64_t i = row * (L * P) + k;
+        gattn[i] = res.x;
+        *reinterpret_cast<float2 *>(gloc + i * 2) = make_float2(res.y, res.z);
+    }
 };
-__device__ __forceinline__ Tile tile_of_block(int M, int tiles_per_image, int rows_per_block)
+
+// Offsets, logits and their gradients are PT = float or T16 (the C ABI's prologue_type); the softmax, the locations and every sum
+// are fp32.
+template <typename PT>
+struct RawIO16 {
+    const float *ref;               // (N, Lq, L, ref_dim), fp32 always: locations are never narrowed
+    const PT *off, *logit;          // (N, Lq, M, L, P, 2), (N, Lq, M, L * P)
+    const unsigned char *mask;      // (N, S) bytes, nonzero = padded pixel, or null
+    int ref_dim;
+    PT *goff, *glogit;              // gradients of off / logit (backward; null in the forward)
+    static constexpr bool kSoftmax = true;      // logit holds raw logits: record() normalises the row across the lanes that own it
+    static constexpr const char *kFwd[3] = {"msda_fwd_h16_fused<1", "msda_fwd_h16_fused<2", "msda_fwd_h16_fused<4"};
+    static constexpr const char *kBwd = "msda_bwd_h16_fused+msda_h16_convert";
+    // the softmax rows (logits, then exponentials) when L * P is no power of two (<= 64: check_fused)
+    static size_t softmax_lds(int rows, int LP) { return (LP & (LP - 1)) == 0 ? 0 : (size_t)2 * rows * LP * sizeof(float); }
+
+    // element access of the raw operands: a 16-bit offset pair is one dword (x in the low half)
+    static constexpr bool kF32 = std::is_same<PT, float>::value;
+    static __device__ __forceinline__ float2 ld_off(const PT *p, int64_t i)
+    {
+        if constexpr (kF32) {
+            return *reinterpret_cast<const float2 *>(p + 2 * i);
+        } else {
+            const unsigned b = *reinterpret_cast<const unsigned *>(p + 2 * i);
+            return make_float2(Cvt<PT>::up(b & 0xffffu), Cvt<PT>::up(b >> 16));
+        }
+    }
+    static __device__ __forceinline__ float ld_logit(const PT *p, int64_t i)
+    {
+        if constexpr (kF32) return p[i];
+        else return ld16(p + i);
+    }
+    static __device__ __forceinline__ void st_off(PT *p, int64_t i, float2 v)
+    {
+        if constexpr (kF32) *reinterpret_cast<float2 *>(p + 2 * i) = v;
+        else *reinterpret_cast<unsigned *>(p + 2 * i) = pack2<PT>(v.x, v.y);
+    }
+    static __device__ __forceinline__ void st_logit(PT *p, int64_t i, float v)
+    {
+        if constexpr (kF32) p[i] = v;
+        else st16(p + i, v);
+    }
+
+    struct TileState {
+        __amdgpu_buffer_rsrc_t rr;      // the image's reference points: Lq * L * ref_dim floats
+        const float *sm_e;              // exp(logit - row max) of the tile's samples in LDS (L * P no power of two)
+    };
+    // The reference point of (query, level) as {x, y, w, h}: one 8-byte buffer load for a point, two for a box -- branch-free: a
+    // point's second load is sent out of range and returns zeros.
+    __device__ __forceinline__ float4 ld_ref(const TileState &ts, int ql) const
+    {
+        const unsigned b = (unsigned)(ql * ref_dim) * 4u;
+        const float2 c = buf_ld2(ts.rr, b), wh = buf_ld2(ts.rr, ref_dim == 4 ? b + 8u : kOob);
+        return make_float4(c.x, c.y, wh.x, wh.y);
+    }
+    // For an L * P whose rows do not line up with the shuffle groups (five levels x four points = 20): exp(logit - row max) of every
+    // sample of the tile into LDS.  sm: 2 x rows x LP floats; the exponentials are sm[rows * LP + s].  Ends with a barrier.
+    __device__ __forceinline__ TileState begin_tile(const Tile t, int rows, int M, int L, int P, int Lq, float *sm) const
+    {
+        const int LP = L * P, total = rows * LP;
+        if (!lp_shuffles(LP)) {
+            for (int s = threadIdx.x; s < total; s += 256) {
+                const int r = s / LP;
+                sm[s] = t.q0 + r < Lq ? ld_logit(logit, (((int64_t)t.n * Lq + t.q0 + r) * M + t.m) * LP + (s - r * LP)) : 0.f;
+            }
+            __syncthreads();
+            for (int s = threadIdx.x; s < total; s += 256) {
+                const float *lr = sm + (s / LP) * LP;
+                float mx = lr[0];
+                for (int j = 1; j < LP; ++j) mx = fmaxf(mx, lr[j]);
+                sm[total + s] = __expf(sm[s] - mx);
+            }
+            __syncthreads();
+        }
+        return TileState{image_rsrc(ref + (int64_t)t.n * Lq * L * ref_dim, (unsigned)(Lq * L * ref_dim) * 4u), sm + total};
+    }
+    // The softmax weight `a` of the sample (fp32, over the row's L * P logits), its location by msda_geom.h's fused_loc_xy, its
+    // corners by sample_setup_oob, and a corner on a padded pixel -> kOob.  Called by ALL threads of the workgroup (the softmax
+    // reduces across lanes); `in`: the thread has a sample slot, `live`: that slot's query row exists.  `a` is kept for samples
+    // off the map too (the softmax backward needs every probability) and is 0 for a row that does not exist.
+    __device__ __forceinline__ bool record(const TileState &ts, const int64_t *__restrict__ shapes, const int64_t *__restrict__ starts,
+                                           bool in, bool live, int n, int q, int64_t row, int r, int k, int l, int S, int L, int P,
+                                           unsigned row_bytes, unsigned (&off)[4], float &lw, float &lh, float &a) const
+    {
+        const int LP = L * P;
+        float2 o = make_float2(0.f, 0.f);
+        float4 rp = make_float4(0.f, 0.f, 0.f, 0.f);
+        float raw = 0.f;
+        int H = 1, W = 1, st = 0;
+        const bool shuf = lp_shuffles(LP);      // (workgroup-uniform)
+        if (live) {
+            o = ld_off(this->off, row * LP + k);
+            if (shuf) raw = ld_logit(logit, row * LP + k);
+            rp = ld_ref(ts, q * L + l);
+            H = (int)shapes[2 * l];
+            W = (int)shapes[2 * l + 1];
+            st = (int)starts[l];
+        }
+        if (shuf) {      // __expf / v_rcp_f32 as the fp32 kernels' row_softmax (msda_fast.h)
+            const float e = __expf(raw - lp_group_max(raw, LP));
+            a = e * fast_rcp(lp_group_sum(e, LP));
+        } else {
+            float sum = 0.f;
+            if (in)
+                for (int j = 0; j < LP; ++j) sum += ts.sm_e[r * LP + j];      // fixed order
+            a = in ? ts.sm_e[r * LP + k] * fast_rcp(sum) : 0.f;
+        }
+        off[0] = off[1] = off[2] = off[3] = kOob;
+        lw = lh = 0.f;
+        if (!live) {
+            a = 0.f;
+            return false;
+        }
+        float x, y;
+        fused_loc_xy(o, rp, ref_dim, P, H, W, x, y);
+        if (!sample_setup_oob(x, y, H, W, st, row_bytes, off, lw, lh)) return false;
+        if (mask) {      // (x, y) -> top-left pixel exactly as sample_setup_oob derives it
+            const int h0 = (int)floorf(sub_rn(mul_rn(y, (float)H), 0.5f)), w0 = (int)floorf(sub_rn(mul_rn(x, (float)W), 0.5f));
+            const int pix = st + h0 * W + w0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int p = pix + (c & 1) + (c >> 1) * W;
+                // (a level table that does not tile [0, S) must not reach past the mask)
+                if (off[c] != kOob && ((unsigned)p >= (unsigned)S || mask[(int64_t)n * S + p] != 0)) off[c] = kOob;
+            }
+        }
+        return true;
+    }
+    // The fused epilogue: the softmax backward grad_logits = a_k (g_k - sum_j a_j g_j) with the row's dot from LDS in a fixed order,
+    // grad_offsets = grad_loc * scale; both rounded once when PT is 16-bit.
+    __device__ __forceinline__ void store(const TileState &ts, int64_t row, int q, int k, int l, int L, int P, int H, int W,
+                                          const float4 res, const float4 *row_res) const
+    {
+        const int LP = L * P;
+        float dot = 0.f;
+        for (int j = 0; j < LP; ++j) dot += row_res[j].w * row_res[j].x;
+        const float2 sc = fused_loc_scale(ld_ref(ts, q * L + l), ref_dim, P, H, W);
+        st_logit(glogit, row * LP + k, res.w * (res.x - dot));
+        st_off(goff, row * LP + k, make_float2(res.y * sc.x, res.z * sc.y));
+    }
+};
+
+// Phase 1 of both fast kernels: one record per sample of the tile's `rows` query rows, built by the policy and handed to
+// put(record index, level, off, lw, lh, a, on the map).  Records of a row are LP + 1 apart: rows land on different LDS banks.
+template <typename IO, typename Put>
+__device__ __forceinline__ void tile_records(const IO &io, const typename IO::TileState &ts, const int64_t *__restrict__ shapes,
+                                             const int64_t *__restrict__ starts, const Tile t, int rows, int S, int M, int L, int Lq,
+                                             int P, Put put)
 {
-    Tile t;
-    const int b = (int)blockIdx.x, r = b / M;
-    t.m = (b % M + r / 64) % M;
-    t.q0 = (r % tiles_per_image) * rows_per_block;
-    t.n = r / tiles_per_image;
-    return t;
+    const int LP = L * P, total = rows * LP;
+    const unsigned row_bytes = (unsigned)(M * kD) * 2u;
+    auto slot = [&](int s, bool in) {      // `in`: s is a sample of the tile
+        const int r = in ? s / LP : 0, k = in ? s - r * LP : 0;
+        const int q = t.q0 + r, l = k / P;
+        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
+        unsigned off[4];
+        float lw, lh, a;
+        const bool on = io.record(ts, shapes, starts, in, in && q < Lq, t.n, q, row, r, k, l, S, L, P, row_bytes, off, lw, lh, a);
+        if (in) put(r * (LP + 1) + k, l, off, lw, lh, a, on);
+    };
+    // (Two loop headers on purpose: as ONE uniform loop with an early exit, the reference contract's SPLIT 2 forward took 68 VGPRs
+    //  instead of 42 and lost a wave -- profiles/msda_h16_one_template.txt.)
+    if constexpr (IO::kSoftmax) {      // the softmax reduces across lanes: every thread walks every trip
+        for (int s0 = 0; s0 < total; s0 += 256) slot(s0 + (int)threadIdx.x, s0 + (int)threadIdx.x < total);
+    } else {
+        for (int s = threadIdx.x; s < total; s += 256) slot(s, true);
+    }
 }
 
-// Phase 2 of the D == 32 forwards (msda_fwd_h16, msda_fwd_h16_fused): gather + weighted sum in fp32 from the tile's LDS records,
-// one 8-byte non-temporal store per lane.
+// Phase 2 of the D == 32 forward: gather + weighted sum in fp32 from the tile's LDS records, one 8-byte non-temporal store per lane.
 template <typename T16, int SPLIT>
 __device__ __forceinline__ void fwd_gather_store(const T16 *__restrict__ value, const int4 *rec_off, const float4 *rec_w, const Tile t,
                                                  int S, int M, int LP, int LPP, int Lq, T16 *__restrict__ out)
@@ -132,51 +323,41 @@ __device__ __forceinline__ void fwd_gather_store(const T16 *__restrict__ value, 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // forward, D == 32.  SPLIT = number of 8-lane groups that share one query row (each takes samples part, part + SPLIT, ...):
-// small query sets still fill the chip.  LDS: (32 / SPLIT) x (L * P + 1) records of 32 bytes.
+// small query sets still fill the chip.  LDS: (32 / SPLIT) x (L * P + 1) records of 32 bytes + IO::softmax_lds.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T16, int SPLIT>
+template <typename T16, typename IO, int SPLIT>
 __global__ __launch_bounds__(256) void msda_fwd_h16(const T16 *__restrict__ value, const int64_t *__restrict__ shapes,
-                                                    const int64_t *__restrict__ starts, const float *__restrict__ loc,
-                                                    const float *__restrict__ attn, int S, int M, int L, int Lq, int P,
-                                                    int tiles_per_image, T16 *__restrict__ out)
+                                                    const int64_t *__restrict__ starts, const IO io, int S, int M, int L, int Lq,
+                                                    int P, int tiles_per_image, T16 *__restrict__ out)
 {
     constexpr int RPB = 32 / SPLIT;
     extern __shared__ float4 smem[];
-    const int LP = L * P, LPP = LP + 1;      // +1 record of padding: rows land on different LDS banks
+    const int LP = L * P, LPP = LP + 1;
     int4 *rec_off = reinterpret_cast<int4 *>(smem);
     float4 *rec_w = smem + RPB * LPP;
     const Tile t = tile_of_block(M, tiles_per_image, RPB);
-    const unsigned row_bytes = (unsigned)(M * kD) * 2u;
+    const auto ts = io.begin_tile(t, RPB, M, L, P, Lq, reinterpret_cast<float *>(smem + 2 * RPB * LPP));
 
-    // ---- phase 1: sample records
-    for (int s = threadIdx.x; s < RPB * LP; s += 256) {
-        const int r = s / LP, k = s - r * LP;
-        const int q = t.q0 + r;
-        unsigned off[4] = {kOob, kOob, kOob, kOob};      // out of range -> the hardware returns zeros
-        float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q < Lq) {
-            const int l = k / P;
-            const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1], st = (int)starts[l];
-            const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
-            const float2 xy = *reinterpret_cast<const float2 *>(loc + (row * LP + k) * 2);
-            const float a = attn[row * LP + k];
-            float lw, lh;
-            if (sample_setup_oob(xy.x, xy.y, H, W, st, row_bytes, off, lw, lh)) {
-                const float hh = 1.f - lh, hw = 1.f - lw;
-                w = make_float4(a * (hh * hw), a * (hh * lw), a * (lh * hw), a * (lh * lw));
-            }
-        }
-        rec_off[r * LPP + k] = make_int4((int)off[0], (int)off[1], (int)off[2], (int)off[3]);
-        rec_w[r * LPP + k] = w;
-    }
+    // ---- phase 1: sample records {4 corner byte offsets, 4 weights}
+    tile_records(io, ts, shapes, starts, t, RPB, S, M, L, Lq, P,
+                 [&](int i, int l, const unsigned (&off)[4], float lw, float lh, float a, bool on) {
+                     (void)l;
+                     float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+                     if (on) {
+                         const float hh = 1.f - lh, hw = 1.f - lw;
+                         w = make_float4(a * (hh * hw), a * (hh * lw), a * (lh * hw), a * (lh * lw));
+                     }
+                     rec_off[i] = make_int4((int)off[0], (int)off[1], (int)off[2], (int)off[3]);
+                     rec_w[i] = w;
+                 });
     __syncthreads();
 
     // ---- phase 2: gather + weighted sum in fp32
     fwd_gather_store<T16, SPLIT>(value, rec_off, rec_w, t, S, M, LP, LPP, Lq, out);
 }
 
-// Row phase of the D == 32 backwards (msda_bwd_h16, msda_bwd_h16_fused): each half-wave walks its rows' LDS records {corner
-// offsets} / {lw, lh, a, level}: fp32 atomics into the workspace, and the record overwritten with {g_attn, g_x, g_y, a}.
+// Row phase of the D == 32 backward: each half-wave walks its rows' LDS records {corner offsets} / {lw, lh, a, level}: fp32
+// atomics into the workspace, and the record overwritten with {g_attn, g_x, g_y, a}.
 template <typename T16>
 __device__ __forceinline__ void bwd_rows(const T16 *__restrict__ gout, const T16 *__restrict__ value, const int4 *rec_off,
                                          float4 *rec_p, const float *lev_w, const float *lev_h, const Tile t, int S, int M, int LP,
@@ -225,60 +406,44 @@ __device__ __forceinline__ void bwd_rows(const T16 *__restrict__ gout, const T16
 // ---------------------------------------------------------------------------------------------------------------------
 // backward, D == 32: rpb query rows per 256-thread workgroup (8 half-waves, each walks rpb / 8 rows), lane = channel.
 // grad_value contributions go into the fp32 workspace `gws` (N * S * M * D floats, zero on entry) with fp32 atomics.
-// LDS: rpb x (L * P + 1) x 2 records of 16 bytes + the level table.
+// LDS: rpb x (L * P + 1) x 2 records of 16 bytes + the level table + IO::softmax_lds.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T16>
+template <typename T16, typename IO>
 __global__ __launch_bounds__(256) void msda_bwd_h16(const T16 *__restrict__ gout, const T16 *__restrict__ value,
                                                     const int64_t *__restrict__ shapes, const int64_t *__restrict__ starts,
-                                                    const float *__restrict__ loc, const float *__restrict__ attn, int S, int M,
-                                                    int L, int Lq, int P, int tiles_per_image, int rpb, float *__restrict__ gws,
-                                                    float *__restrict__ gloc, float *__restrict__ gattn)
+                                                    const IO io, int S, int M, int L, int Lq, int P, int tiles_per_image, int rpb,
+                                                    float *__restrict__ gws)
 {
     extern __shared__ float4 smem[];
     const int LP = L * P, LPP = LP + 1;
     int4 *rec_off = reinterpret_cast<int4 *>(smem);
-    float4 *rec_p = smem + rpb * LPP;      // {lw, lh, a, level}; overwritten with {g_attn, g_x, g_y, -}
+    float4 *rec_p = smem + rpb * LPP;      // {lw, lh, a, level}; overwritten with {g_attn, g_x, g_y, a}
     float *lev_w = reinterpret_cast<float *>(smem + 2 * rpb * LPP), *lev_h = lev_w + kMaxLevels;
     const Tile t = tile_of_block(M, tiles_per_image, rpb);
-    const unsigned row_bytes = (unsigned)(M * kD) * 2u;
     if (threadIdx.x < L) {
         lev_h[threadIdx.x] = (float)shapes[2 * threadIdx.x];
         lev_w[threadIdx.x] = (float)shapes[2 * threadIdx.x + 1];
     }
-    for (int s = threadIdx.x; s < rpb * LP; s += 256) {
-        const int r = s / LP, k = s - r * LP;
-        const int q = t.q0 + r;
-        unsigned off[4] = {kOob, kOob, kOob, kOob};
-        const int l = k / P;
-        float4 pr = make_float4(0.f, 0.f, 0.f, __int_as_float(l));
-        if (q < Lq) {
-            const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1], st = (int)starts[l];
-            const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
-            const float2 xy = *reinterpret_cast<const float2 *>(loc + (row * LP + k) * 2);
-            pr.z = attn[row * LP + k];
-            float lw, lh;
-            if (sample_setup_oob(xy.x, xy.y, H, W, st, row_bytes, off, lw, lh)) {
-                pr.x = lw;
-                pr.y = lh;
-            }
-        }
-        rec_off[r * LPP + k] = make_int4((int)off[0], (int)off[1], (int)off[2], (int)off[3]);
-        rec_p[r * LPP + k] = pr;
-    }
+    const auto ts = io.begin_tile(t, rpb, M, L, P, Lq, lev_h + kMaxLevels);
+    tile_records(io, ts, shapes, starts, t, rpb, S, M, L, Lq, P,
+                 [&](int i, int l, const unsigned (&off)[4], float lw, float lh, float a, bool on) {
+                     (void)on;
+                     rec_off[i] = make_int4((int)off[0], (int)off[1], (int)off[2], (int)off[3]);
+                     rec_p[i] = make_float4(lw, lh, a, __int_as_float(l));
+                 });
     __syncthreads();
 
     bwd_rows<T16>(gout, value, rec_off, rec_p, lev_w, lev_h, t, S, M, LP, LPP, Lq, rpb, gws);
     __syncthreads();
 
-    // ---- coalesced write-back of grad_attn_weight / grad_sampling_loc (fp32, unrounded)
+    // ---- coalesced write-back of the two small gradients, in the policy's form
     for (int s = threadIdx.x; s < rpb * LP; s += 256) {
-        const int rr = s / LP, k = s - rr * LP;
-        const int qq = t.q0 + rr;
-        if (qq >= Lq) continue;
-        const int64_t row = ((int64_t)t.n * Lq + qq) * M + t.m;
-        const float4 res = rec_p[rr * LPP + k];
-        gattn[row * LP + k] = res.x;
-        *reinterpret_cast<float2 *>(gloc + (row * LP + k) * 2) = make_float2(res.y, res.z);
+        const int r = s / LP, k = s - r * LP;
+        const int q = t.q0 + r;
+        if (q >= Lq) continue;
+        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
+        const int l = k / P;
+        io.store(ts, row, q, k, l, L, P, (int)lev_h[l], (int)lev_w[l], rec_p[r * LPP + k], rec_p + r * LPP);
     }
 }
 
@@ -301,246 +466,6 @@ __global__ __launch_bounds__(256) void msda_h16_convert(const float *__restrict_
     }
     const int64_t end = i + 8 < count ? i + 8 : count;
     for (int64_t e = i; e < end; ++e) st16(dst + e, ws[e]);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Fused prologue / epilogue on a 16-bit value map: the kernels above with the sample records built from the
-// fp32 reference points, the RAW sampling offsets and the RAW attention logits, and the padding mask as bytes -- what RawIO
-// (msda_fast.h) is to the fp32 kernels.  Offsets, logits and their gradients are PT = float or T16 (the C ABI's prologue_type);
-// the softmax, the locations and every sum are fp32.
-// ---------------------------------------------------------------------------------------------------------------------
-template <typename PT>
-struct Prologue {
-    const float *ref;               // (N, Lq, L, ref_dim), fp32 always: locations are never narrowed
-    const PT *off, *logit;          // (N, Lq, M, L, P, 2), (N, Lq, M, L * P)
-    const unsigned char *mask;      // (N, S) bytes, nonzero = padded pixel, or null
-    int ref_dim;
-};
-// element access of the raw operands: a 16-bit offset pair is one dword (x in the low half)
-template <typename PT>
-struct RawOp {
-    static __device__ __forceinline__ float2 ld_off(const PT *p, int64_t i)
-    {
-        const unsigned b = *reinterpret_cast<const unsigned *>(p + 2 * i);
-        return make_float2(Cvt<PT>::up(b & 0xffffu), Cvt<PT>::up(b >> 16));
-    }
-    static __device__ __forceinline__ float ld_logit(const PT *p, int64_t i) { return ld16(p + i); }
-    static __device__ __forceinline__ void st_off(PT *p, int64_t i, float2 v) { *reinterpret_cast<unsigned *>(p + 2 * i) = pack2<PT>(v.x, v.y); }
-    static __device__ __forceinline__ void st_logit(PT *p, int64_t i, float v) { st16(p + i, v); }
-};
-template <>
-struct RawOp<float> {
-    static __device__ __forceinline__ float2 ld_off(const float *p, int64_t i) { return *reinterpret_cast<const float2 *>(p + 2 * i); }
-    static __device__ __forceinline__ float ld_logit(const float *p, int64_t i) { return p[i]; }
-    static __device__ __forceinline__ void st_off(float *p, int64_t i, float2 v) { *reinterpret_cast<float2 *>(p + 2 * i) = v; }
-    static __device__ __forceinline__ void st_logit(float *p, int64_t i, float v) { p[i] = v; }
-};
-
-// Reductions over a lane-aligned group of LP threads, LP a power of two <= 64 (msda_fast.h lp_group_max / lp_group_sum: DPP inside
-// a 16-lane row, shuffles beyond); every lane of the group gets the result.
-__device__ __forceinline__ bool lp_shuffles(int LP) { return (LP & (LP - 1)) == 0 && LP <= 64; }
-__device__ __forceinline__ float lp_group_sum(float x, int LP)
-{
-    if (LP >= 2) x += dpp_mov<0xB1>(x);
-    if (LP >= 4) x += dpp_mov<0x4E>(x);
-    if (LP >= 8) x += dpp_mov<0x141>(x);
-    if (LP >= 16) x += dpp_mov<0x140>(x);
-    if (LP >= 32) x += __shfl_xor(x, 16, 64);
-    if (LP >= 64) x += __shfl_xor(x, 32, 64);
-    return x;
-}
-__device__ __forceinline__ float lp_group_max(float x, int LP)
-{
-    if (LP >= 2) x = fmaxf(x, dpp_mov<0xB1>(x));
-    if (LP >= 4) x = fmaxf(x, dpp_mov<0x4E>(x));
-    if (LP >= 8) x = fmaxf(x, dpp_mov<0x141>(x));
-    if (LP >= 16) x = fmaxf(x, dpp_mov<0x140>(x));
-    if (LP >= 32) x = fmaxf(x, __shfl_xor(x, 16, 64));
-    if (LP >= 64) x = fmaxf(x, __shfl_xor(x, 32, 64));
-    return x;
-}
-
-// The reference point of (query, level) as {x, y, w, h}: one 8-byte buffer load for a point, two for a box -- branch-free: a
-// point's second load is sent out of range and returns zeros.  `rr` covers the image's Lq * L * ref_dim floats.
-__device__ __forceinline__ float4 ld_ref(__amdgpu_buffer_rsrc_t rr, int ql, int ref_dim)
-{
-    const unsigned b = (unsigned)(ql * ref_dim) * 4u;
-    const float2 c = buf_ld2(rr, b), wh = buf_ld2(rr, ref_dim == 4 ? b + 8u : kOob);
-    return make_float4(c.x, c.y, wh.x, wh.y);
-}
-
-// exp(logit - row max) of every sample of the tile into LDS, for an L * P whose rows do not line up with the shuffle groups
-// (five levels x four points = 20).  sm: 2 x rows x LP floats; the exponentials are sm[rows * LP + s].  Ends with a barrier.
-template <typename PT>
-__device__ __forceinline__ void tile_exp_to_lds(const PT *logit, const Tile t, int rows, int M, int LP, int Lq, float *sm)
-{
-    const int total = rows * LP;
-    for (int s = threadIdx.x; s < total; s += 256) {
-        const int r = s / LP;
-        sm[s] = t.q0 + r < Lq ? RawOp<PT>::ld_logit(logit, (((int64_t)t.n * Lq + t.q0 + r) * M + t.m) * LP + (s - r * LP)) : 0.f;
-    }
-    __syncthreads();
-    for (int s = threadIdx.x; s < total; s += 256) {
-        const float *lr = sm + (s / LP) * LP;
-        float mx = lr[0];
-        for (int j = 1; j < LP; ++j) mx = fmaxf(mx, lr[j]);
-        sm[total + s] = __expf(sm[s] - mx);
-    }
-    __syncthreads();
-}
-
-// One sample record of a tile from the raw operands: the softmax weight `a` of the sample (fp32, over the row's L * P logits),
-// its location by msda_geom.h's fused_loc_xy, its corners by sample_setup_oob, and a corner on a padded pixel -> kOob (never
-// loaded, no gradient).  Called by ALL threads of the workgroup (the softmax reduces across lanes); `in`: the thread has a
-// sample slot, `live`: that slot's query row exists.  Returns whether the sample is on the map.
-template <typename PT>
-__device__ __forceinline__ bool fused_record(const Prologue<PT> &pg, __amdgpu_buffer_rsrc_t rr, const int64_t *__restrict__ shapes,
-                                             const int64_t *__restrict__ starts, const float *sm_e, bool in, bool live, int n, int q,
-                                             int64_t row, int r, int k, int S, int L, int P, unsigned row_bytes, unsigned (&off)[4],
-                                             float &lw, float &lh, float &a)
-{
-    const int LP = L * P, l = k / P;
-    float2 o = make_float2(0.f, 0.f);
-    float4 rp = make_float4(0.f, 0.f, 0.f, 0.f);
-    float raw = 0.f;
-    int H = 1, W = 1, st = 0;
-    const bool shuf = lp_shuffles(LP);      // (workgroup-uniform)
-    if (live) {
-        o = RawOp<PT>::ld_off(pg.off, row * LP + k);
-        if (shuf) raw = RawOp<PT>::ld_logit(pg.logit, row * LP + k);
-        rp = ld_ref(rr, q * L + l, pg.ref_dim);
-        H = (int)shapes[2 * l];
-        W = (int)shapes[2 * l + 1];
-        st = (int)starts[l];
-    }
-    if (shuf) {      // __expf / v_rcp_f32 as the fp32 kernels' row_softmax (msda_fast.h)
-        const float e = __expf(raw - lp_group_max(raw, LP));
-        a = e * fast_rcp(lp_group_sum(e, LP));
-    } else {
-        float sum = 0.f;
-        if (in)
-            for (int j = 0; j < LP; ++j) sum += sm_e[r * LP + j];      // fixed order
-        a = in ? sm_e[r * LP + k] * fast_rcp(sum) : 0.f;
-    }
-    off[0] = off[1] = off[2] = off[3] = kOob;
-    lw = lh = 0.f;
-    if (!live) return false;
-    float x, y;
-    fused_loc_xy(o, rp, pg.ref_dim, P, H, W, x, y);
-    if (!sample_setup_oob(x, y, H, W, st, row_bytes, off, lw, lh)) return false;
-    if (pg.mask) {      // (x, y) -> top-left pixel exactly as sample_setup_oob derives it
-        const int h0 = (int)floorf(sub_rn(mul_rn(y, (float)H), 0.5f)), w0 = (int)floorf(sub_rn(mul_rn(x, (float)W), 0.5f));
-        const int pix = st + h0 * W + w0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int p = pix + (c & 1) + (c >> 1) * W;
-            // (a level table that does not tile [0, S) must not reach past the mask)
-            if (off[c] != kOob && ((unsigned)p >= (unsigned)S || pg.mask[(int64_t)n * S + p] != 0)) off[c] = kOob;
-        }
-    }
-    return true;
-}
-
-// forward: msda_fwd_h16 with phase 1 from the raw operands.  LDS: the records + 2 x RPB x L * P floats when L * P is no power of two.
-template <typename T16, typename PT, int SPLIT>
-__global__ __launch_bounds__(256) void msda_fwd_h16_fused(const T16 *__restrict__ value, const int64_t *__restrict__ shapes,
-                                                          const int64_t *__restrict__ starts, const Prologue<PT> pg, int S, int M,
-                                                          int L, int Lq, int P, int tiles_per_image, T16 *__restrict__ out)
-{
-    constexpr int RPB = 32 / SPLIT;
-    extern __shared__ float4 smem[];
-    const int LP = L * P, LPP = LP + 1, total = RPB * LP;
-    int4 *rec_off = reinterpret_cast<int4 *>(smem);
-    float4 *rec_w = smem + RPB * LPP;
-    float *sm = reinterpret_cast<float *>(smem + 2 * RPB * LPP);
-    const Tile t = tile_of_block(M, tiles_per_image, RPB);
-    const unsigned row_bytes = (unsigned)(M * kD) * 2u;
-    if (!lp_shuffles(LP)) tile_exp_to_lds<PT>(pg.logit, t, RPB, M, LP, Lq, sm);
-    const __amdgpu_buffer_rsrc_t rr = image_rsrc(pg.ref + (int64_t)t.n * Lq * L * pg.ref_dim, (unsigned)(Lq * L * pg.ref_dim) * 4u);
-
-    // ---- phase 1: sample records (every thread walks every trip: the softmax reduces across lanes)
-    for (int s0 = 0; s0 < total; s0 += 256) {
-        const int s = s0 + (int)threadIdx.x;
-        const bool in = s < total;
-        const int r = in ? s / LP : 0, k = in ? s - r * LP : 0;
-        const int q = t.q0 + r;
-        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
-        unsigned off[4];
-        float lw, lh, a;
-        float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (fused_record<PT>(pg, rr, shapes, starts, sm + total, in, in && q < Lq, t.n, q, row, r, k, S, L, P, row_bytes, off, lw, lh, a)) {
-            const float hh = 1.f - lh, hw = 1.f - lw;
-            w = make_float4(a * (hh * hw), a * (hh * lw), a * (lh * hw), a * (lh * lw));
-        }
-        if (in) {
-            rec_off[r * LPP + k] = make_int4((int)off[0], (int)off[1], (int)off[2], (int)off[3]);
-            rec_w[r * LPP + k] = w;
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 2: gather + weighted sum in fp32
-    fwd_gather_store<T16, SPLIT>(value, rec_off, rec_w, t, S, M, LP, LPP, Lq, out);
-}
-
-// backward: msda_bwd_h16 with the records from the raw operands and the fused epilogue in the write-back: the softmax backward
-// grad_logits = a_k (g_k - sum_j a_j g_j) with the row's dot from LDS in a fixed order, grad_offsets = grad_loc * scale; both
-// rounded once when PT is 16-bit.  LDS: as msda_bwd_h16 + 2 x rpb x L * P floats when L * P is no power of two.
-template <typename T16, typename PT>
-__global__ __launch_bounds__(256) void msda_bwd_h16_fused(const T16 *__restrict__ gout, const T16 *__restrict__ value,
-                                                          const int64_t *__restrict__ shapes, const int64_t *__restrict__ starts,
-                                                          const Prologue<PT> pg, int S, int M, int L, int Lq, int P,
-                                                          int tiles_per_image, int rpb, float *__restrict__ gws, PT *__restrict__ goff,
-                                                          PT *__restrict__ glogit)
-{
-    extern __shared__ float4 smem[];
-    const int LP = L * P, LPP = LP + 1, total = rpb * LP;
-    int4 *rec_off = reinterpret_cast<int4 *>(smem);
-    float4 *rec_p = smem + rpb * LPP;      // {lw, lh, a, level}; overwritten with {g_attn, g_x, g_y, a}
-    float *lev_w = reinterpret_cast<float *>(smem + 2 * rpb * LPP), *lev_h = lev_w + kMaxLevels;
-    float *sm = lev_h + kMaxLevels;
-    const Tile t = tile_of_block(M, tiles_per_image, rpb);
-    const unsigned row_bytes = (unsigned)(M * kD) * 2u;
-    if (threadIdx.x < L) {
-        lev_h[threadIdx.x] = (float)shapes[2 * threadIdx.x];
-        lev_w[threadIdx.x] = (float)shapes[2 * threadIdx.x + 1];
-    }
-    if (!lp_shuffles(LP)) tile_exp_to_lds<PT>(pg.logit, t, rpb, M, LP, Lq, sm);
-    const __amdgpu_buffer_rsrc_t rr = image_rsrc(pg.ref + (int64_t)t.n * Lq * L * pg.ref_dim, (unsigned)(Lq * L * pg.ref_dim) * 4u);
-    for (int s0 = 0; s0 < total; s0 += 256) {
-        const int s = s0 + (int)threadIdx.x;
-        const bool in = s < total;
-        const int r = in ? s / LP : 0, k = in ? s - r * LP : 0;
-        const int q = t.q0 + r;
-        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
-        unsigned off[4];
-        float lw, lh, a;
-        fused_record<PT>(pg, rr, shapes, starts, sm + total, in, in && q < Lq, t.n, q, row, r, k, S, L, P, row_bytes, off, lw, lh, a);
-        if (in) {      // `a` is kept for skipped samples too: the softmax backward needs every probability
-            rec_off[r * LPP + k] = make_int4((int)off[0], (int)off[1], (int)off[2], (int)off[3]);
-            rec_p[r * LPP + k] = make_float4(lw, lh, q < Lq ? a : 0.f, __int_as_float(k / P));
-        }
-    }
-    __syncthreads();
-
-    bwd_rows<T16>(gout, value, rec_off, rec_p, lev_w, lev_h, t, S, M, LP, LPP, Lq, rpb, gws);
-    __syncthreads();
-
-    // ---- coalesced write-back of grad_attn_logits / grad_sampling_offsets, each in PT
-    for (int s = threadIdx.x; s < total; s += 256) {
-        const int r = s / LP, k = s - r * LP;
-        const int q = t.q0 + r;
-        if (q >= Lq) continue;
-        const int64_t row = ((int64_t)t.n * Lq + q) * M + t.m;
-        const float4 *rowp = rec_p + r * LPP;
-        const float4 res = rowp[k];      // {d/d a_k, d/d loc.x, d/d loc.y, a_k}
-        float dot = 0.f;
-        for (int j = 0; j < LP; ++j) dot += rowp[j].w * rowp[j].x;
-        const int l = k / P;
-        const float2 sc = fused_loc_scale(ld_ref(rr, q * L + l, pg.ref_dim), pg.ref_dim, P, (int)lev_h[l], (int)lev_w[l]);
-        RawOp<PT>::st_logit(glogit, row * LP + k, res.w * (res.x - dot));
-        RawOp<PT>::st_off(goff, row * LP + k, make_float2(res.y * sc.x, res.z * sc.y));
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -647,6 +572,10 @@ __global__ __launch_bounds__(256) void msda_bwd_h16_generic(const T16 *__restric
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
+struct Dims {
+    int N, S, M, D, L, Lq, P;
+};
+
 int check_common(const void *value, const void *shapes, const void *starts, const void *loc, const void *attn, int dtype, int N,
                  int S, int M, int D, int L, int Lq, int P)
 {
@@ -672,73 +601,96 @@ bool fast_ok(const void *a, const void *b, const void *c, int S, int M, int D, i
            (int64_t)S * M * kD * 2 < (int64_t)0xFFFFF000u;
 }
 
-int pick_split(int N, int Lq, int M)      // as the fp32 forward (msda_dispatch.h pick_split): small query sets spread a row over more lanes
+// LDS of a fast kernel with `rows` query rows: the records (+ the backward's level table) + what the policy's softmax takes
+template <typename IO>
+size_t fast_lds(int rows, int LP, bool backward)
 {
-    const int64_t wg32 = (int64_t)N * M * ((Lq + 31) / 32);
-    return wg32 >= 2048 ? 1 : (wg32 >= 1024 ? 2 : 4);
+    return (size_t)rows * (LP + 1) * 32 + (backward ? 2 * kMaxLevels * sizeof(float) : 0) + IO::softmax_lds(rows, LP);
 }
 
-template <typename T16>
-int forward_impl(hipStream_t st, const T16 *value, const int64_t *shapes, const int64_t *starts, const float *loc, const float *attn,
-                 int N, int S, int M, int D, int L, int Lq, int P, T16 *out)
+// `what`: the C-ABI entry, for the error texts
+template <typename T16, typename IO>
+int launch_fast_forward(hipStream_t st, const T16 *value, const int64_t *shapes, const int64_t *starts, const IO &io, const Dims &d,
+                        T16 *out, const char *what)
 {
-    if (!fast_ok(value, out, loc, S, M, D, L, P)) {
-        const int64_t rows = (int64_t)N * Lq * M;
-        hipLaunchKernelGGL(msda_fwd_h16_generic<T16>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, value, shapes, starts, loc,
-                           attn, N, S, M, D, L, Lq, P, out);
-        g_last_kernels = "msda_fwd_h16_generic";
-        return semidetr::launch_status("msda_fwd_h16_generic");
-    }
-    int split = pick_split(N, Lq, M);
-    while (split < 4 && (size_t)(32 / split) * (L * P + 1) * 32 > 64 * 1024) split *= 2;      // wide rows: fewer per workgroup
+    const int LP = d.L * d.P;
+    int split = semidetr::pick_split(0, d.N, d.Lq, d.M);      // the fp32 forward's rule
+    while (split < 4 && fast_lds<IO>(32 / split, LP, false) > 64 * 1024) split *= 2;      // wide rows: fewer per workgroup
     const int rpb = 32 / split;
-    const int tiles = (Lq + rpb - 1) / rpb;
-    SEMIDETR_REQUIRE((int64_t)N * tiles * M < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_forward_h16: grid too large");
-    const size_t lds = (size_t)rpb * (L * P + 1) * 32;
-    const dim3 grid((unsigned)((int64_t)N * tiles * M));
-    if (split == 1)
-        hipLaunchKernelGGL((msda_fwd_h16<T16, 1>), grid, dim3(256), lds, st, value, shapes, starts, loc, attn, S, M, L, Lq, P, tiles, out);
-    else if (split == 2)
-        hipLaunchKernelGGL((msda_fwd_h16<T16, 2>), grid, dim3(256), lds, st, value, shapes, starts, loc, attn, S, M, L, Lq, P, tiles, out);
-    else
-        hipLaunchKernelGGL((msda_fwd_h16<T16, 4>), grid, dim3(256), lds, st, value, shapes, starts, loc, attn, S, M, L, Lq, P, tiles, out);
-    g_last_kernels = split == 1 ? "msda_fwd_h16<1" : (split == 2 ? "msda_fwd_h16<2" : "msda_fwd_h16<4");
-    return semidetr::launch_status("msda_fwd_h16");
+    const int tiles = (d.Lq + rpb - 1) / rpb;
+    SEMIDETR_REQUIRE((int64_t)d.N * tiles * d.M < INT32_MAX, SEMIDETR_E_TOOLARGE, "%s: grid too large", what);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((int64_t)d.N * tiles * d.M)), dim3(256), fast_lds<IO>(rpb, LP, false), st, value, shapes,
+                           starts, io, d.S, d.M, d.L, d.Lq, d.P, tiles, out);
+    };
+    if (split == 1) launch(&msda_fwd_h16<T16, IO, 1>);
+    else if (split == 2) launch(&msda_fwd_h16<T16, IO, 2>);
+    else launch(&msda_fwd_h16<T16, IO, 4>);
+    g_last_kernels = IO::kFwd[split >> 1];
+    return semidetr::launch_status(g_last_kernels);
 }
 
-template <typename T16>
-int backward_impl(hipStream_t st, const T16 *gout, const T16 *value, const int64_t *shapes, const int64_t *starts, const float *loc,
-                  const float *attn, int N, int S, int M, int D, int L, int Lq, int P, float *ws, T16 *gvalue, float *gloc,
-                  float *gattn)
+template <typename T16, typename IO>
+int launch_fast_backward(hipStream_t st, const T16 *gout, const T16 *value, const int64_t *shapes, const int64_t *starts, const IO &io,
+                         const Dims &d, float *ws, const char *what)
 {
-    const int64_t count = (int64_t)N * S * M * D;
-    const char *name;
-    if (!fast_ok(value, gout, loc, S, M, D, L, P) || (((uintptr_t)gloc) & 7) != 0) {
-        const int64_t rows = (int64_t)N * Lq * M;
-        hipLaunchKernelGGL(msda_bwd_h16_generic<T16>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, gout, value, shapes, starts,
-                           loc, attn, N, S, M, D, L, Lq, P, ws, gloc, gattn);
-        name = "msda_bwd_h16_generic+msda_h16_convert";
-    } else {
-        // 32 query rows per workgroup, 8 when that would not fill the chip or 32 rows of records would not fit 64 KB of LDS
-        const int rpb = ((int64_t)N * M * ((Lq + 31) / 32) >= 1024 &&
-                         (size_t)32 * (L * P + 1) * 32 + 2 * kMaxLevels * sizeof(float) <= 64 * 1024) ? 32 : 8;
-        const int tiles = (Lq + rpb - 1) / rpb;
-        SEMIDETR_REQUIRE((int64_t)N * tiles * M < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_backward_h16: grid too large");
-        const size_t lds = (size_t)rpb * (L * P + 1) * 32 + 2 * kMaxLevels * sizeof(float);
-        if (int rc = semidetr::allow_big_lds(&msda_bwd_h16<T16>, lds, "msda_backward_h16")) return rc;      // only L * P = 254 at 8 rows
-        hipLaunchKernelGGL(msda_bwd_h16<T16>, dim3((unsigned)((int64_t)N * tiles * M)), dim3(256), lds, st, gout, value, shapes, starts,
-                           loc, attn, S, M, L, Lq, P, tiles, rpb, ws, gloc, gattn);
-        name = "msda_bwd_h16+msda_h16_convert";
-    }
-    if (int rc = semidetr::launch_status(name)) return rc;
+    const int LP = d.L * d.P;
+    // 32 query rows per workgroup, 8 when that would not fill the chip or 32 rows of records would not fit 64 KB of LDS
+    const int rpb = ((int64_t)d.N * d.M * ((d.Lq + 31) / 32) >= 1024 && fast_lds<IO>(32, LP, true) <= 64 * 1024) ? 32 : 8;
+    const int tiles = (d.Lq + rpb - 1) / rpb;
+    SEMIDETR_REQUIRE((int64_t)d.N * tiles * d.M < INT32_MAX, SEMIDETR_E_TOOLARGE, "%s: grid too large", what);
+    const size_t lds = fast_lds<IO>(rpb, LP, true);
+    // (a grant is asked for only above 64 KB: L * P = 254 at 8 rows, which only the reference contract admits)
+    if (int rc = semidetr::allow_big_lds(&msda_bwd_h16<T16, IO>, lds, what)) return rc;
+    hipLaunchKernelGGL((msda_bwd_h16<T16, IO>), dim3((unsigned)((int64_t)d.N * tiles * d.M)), dim3(256), lds, st, gout, value, shapes, starts,
+                       io, d.S, d.M, d.L, d.Lq, d.P, tiles, rpb, ws);
+    return semidetr::launch_status(IO::kBwd);
+}
+
+// The backward's last launch: workspace -> grad_value.  `kernels`: what the whole backward reports as its last kernels.
+template <typename T16>
+int convert_grad_value(hipStream_t st, const float *ws, const Dims &d, T16 *gvalue, const char *kernels, const char *what)
+{
+    const int64_t count = (int64_t)d.N * d.S * d.M * d.D;
     const int64_t blocks = (count + 2047) / 2048;
-    SEMIDETR_REQUIRE(blocks < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_backward_h16: grad_value too large");
+    SEMIDETR_REQUIRE(blocks < INT32_MAX, SEMIDETR_E_TOOLARGE, "%s: grad_value too large", what);
     if ((((uintptr_t)ws | (uintptr_t)gvalue) & 15) == 0)
         hipLaunchKernelGGL((msda_h16_convert<T16, true>), dim3((unsigned)blocks), dim3(256), 0, st, ws, count, gvalue);
     else
         hipLaunchKernelGGL((msda_h16_convert<T16, false>), dim3((unsigned)blocks), dim3(256), 0, st, ws, count, gvalue);
-    g_last_kernels = name;
+    g_last_kernels = kernels;
     return semidetr::launch_status("msda_h16_convert");
+}
+
+// ---- reference contract: the fast kernels where fast_ok, the generic ones otherwise
+template <typename T16>
+int forward_impl(hipStream_t st, const T16 *value, const int64_t *shapes, const int64_t *starts, const LocAttnIO16 &io, const Dims &d,
+                 T16 *out)
+{
+    if (fast_ok(value, out, io.loc, d.S, d.M, d.D, d.L, d.P))
+        return launch_fast_forward(st, value, shapes, starts, io, d, out, "msda_forward_h16");
+    const int64_t rows = (int64_t)d.N * d.Lq * d.M;
+    hipLaunchKernelGGL(msda_fwd_h16_generic<T16>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, value, shapes, starts, io.loc, io.attn,
+                       d.N, d.S, d.M, d.D, d.L, d.Lq, d.P, out);
+    g_last_kernels = "msda_fwd_h16_generic";
+    return semidetr::launch_status("msda_fwd_h16_generic");
+}
+
+template <typename T16>
+int backward_impl(hipStream_t st, const T16 *gout, const T16 *value, const int64_t *shapes, const int64_t *starts, const LocAttnIO16 &io,
+                  const Dims &d, float *ws, T16 *gvalue)
+{
+    const char *name = LocAttnIO16::kBwd;
+    if (fast_ok(value, gout, io.loc, d.S, d.M, d.D, d.L, d.P) && (((uintptr_t)io.gloc) & 7) == 0) {
+        if (int rc = launch_fast_backward(st, gout, value, shapes, starts, io, d, ws, "msda_backward_h16")) return rc;
+    } else {
+        const int64_t rows = (int64_t)d.N * d.Lq * d.M;
+        hipLaunchKernelGGL(msda_bwd_h16_generic<T16>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, gout, value, shapes, starts, io.loc,
+                           io.attn, d.N, d.S, d.M, d.D, d.L, d.Lq, d.P, ws, io.gloc, io.gattn);
+        name = "msda_bwd_h16_generic+msda_h16_convert";
+        if (int rc = semidetr::launch_status(name)) return rc;
+    }
+    return convert_grad_value(st, ws, d, gvalue, name, "msda_backward_h16");
 }
 
 // ---- fused prologue / epilogue: the fast kernels or SEMIDETR_E_BADARG (there is no generic fused kernel)
@@ -751,14 +703,14 @@ struct FusedArgs {
     int prologue_type;
     const unsigned char *mask;
     int N, S, M, D, L, Lq, P;
+    Dims dims() const { return Dims{N, S, M, D, L, Lq, P}; }
+    template <typename PT>
+    RawIO16<PT> io(void *goff, void *glogit) const
+    {
+        return RawIO16<PT>{ref, static_cast<const PT *>(off), static_cast<const PT *>(logit), mask, ref_dim, static_cast<PT *>(goff),
+                           static_cast<PT *>(glogit)};
+    }
 };
-
-// LDS of a fused kernel with `rows` query rows: the records (+ the backward's level table) + the softmax rows when L * P is no power of two
-size_t fused_lds(int rows, int LP, bool backward)
-{
-    const bool shuf = (LP & (LP - 1)) == 0;
-    return (size_t)rows * (LP + 1) * 32 + (backward ? 2 * kMaxLevels * sizeof(float) : 0) + (shuf ? 0 : (size_t)2 * rows * LP * sizeof(float));
-}
 
 int check_fused(const FusedArgs &a, int dtype, const void *io16, const char *what)
 {
@@ -783,51 +735,18 @@ int check_fused(const FusedArgs &a, int dtype, const void *io16, const char *wha
     return SEMIDETR_OK;
 }
 
-template <typename T16, typename PT>
-int fused_forward_impl(hipStream_t st, const FusedArgs &a, T16 *out)
+// The run-time dtype and prologue_type as types: f(Type<T16>, Type<PT>) with T16 = __half | __hip_bfloat16 and PT = float
+// (SEMIDETR_ROW_F32) | T16.  Both checked by the caller; the reference-contract entries have no PT and pass SEMIDETR_ROW_F32.
+template <typename T>
+struct Type {
+    using type = T;
+};
+template <typename F>
+int with_types(int dtype, int prologue_type, F f)
 {
-    const Prologue<PT> pg = {a.ref, static_cast<const PT *>(a.off), static_cast<const PT *>(a.logit), a.mask, a.ref_dim};
-    const T16 *value = static_cast<const T16 *>(a.value);
-    const int LP = a.L * a.P;
-    int split = pick_split(a.N, a.Lq, a.M);
-    while (split < 4 && fused_lds(32 / split, LP, false) > 64 * 1024) split *= 2;
-    const int rpb = 32 / split;
-    const int tiles = (a.Lq + rpb - 1) / rpb;
-    SEMIDETR_REQUIRE((int64_t)a.N * tiles * a.M < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_fused_forward_h16: grid too large");
-    const size_t lds = fused_lds(rpb, LP, false);
-    const dim3 grid((unsigned)((int64_t)a.N * tiles * a.M));
-    if (split == 1)
-        hipLaunchKernelGGL((msda_fwd_h16_fused<T16, PT, 1>), grid, dim3(256), lds, st, value, a.shapes, a.starts, pg, a.S, a.M, a.L, a.Lq, a.P, tiles, out);
-    else if (split == 2)
-        hipLaunchKernelGGL((msda_fwd_h16_fused<T16, PT, 2>), grid, dim3(256), lds, st, value, a.shapes, a.starts, pg, a.S, a.M, a.L, a.Lq, a.P, tiles, out);
-    else
-        hipLaunchKernelGGL((msda_fwd_h16_fused<T16, PT, 4>), grid, dim3(256), lds, st, value, a.shapes, a.starts, pg, a.S, a.M, a.L, a.Lq, a.P, tiles, out);
-    g_last_kernels = split == 1 ? "msda_fwd_h16_fused<1" : (split == 2 ? "msda_fwd_h16_fused<2" : "msda_fwd_h16_fused<4");
-    return semidetr::launch_status("msda_fwd_h16_fused");
-}
-
-template <typename T16, typename PT>
-int fused_backward_impl(hipStream_t st, const FusedArgs &a, const T16 *gout, float *ws, T16 *gvalue, void *goff, void *glogit)
-{
-    const Prologue<PT> pg = {a.ref, static_cast<const PT *>(a.off), static_cast<const PT *>(a.logit), a.mask, a.ref_dim};
-    const int LP = a.L * a.P;
-    // 32 query rows per workgroup, 8 when that would not fill the chip or 32 rows would not fit 64 KB of LDS (as backward_impl)
-    const int rpb = ((int64_t)a.N * a.M * ((a.Lq + 31) / 32) >= 1024 && fused_lds(32, LP, true) <= 64 * 1024) ? 32 : 8;
-    const int tiles = (a.Lq + rpb - 1) / rpb;
-    SEMIDETR_REQUIRE((int64_t)a.N * tiles * a.M < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_fused_backward_h16: grid too large");
-    hipLaunchKernelGGL((msda_bwd_h16_fused<T16, PT>), dim3((unsigned)((int64_t)a.N * tiles * a.M)), dim3(256), fused_lds(rpb, LP, true), st, gout,
-                       static_cast<const T16 *>(a.value), a.shapes, a.starts, pg, a.S, a.M, a.L, a.Lq, a.P, tiles, rpb, ws,
-                       static_cast<PT *>(goff), static_cast<PT *>(glogit));
-    if (int rc = semidetr::launch_status("msda_bwd_h16_fused")) return rc;
-    const int64_t count = (int64_t)a.N * a.S * a.M * a.D;
-    const int64_t blocks = (count + 2047) / 2048;
-    SEMIDETR_REQUIRE(blocks < INT32_MAX, SEMIDETR_E_TOOLARGE, "msda_fused_backward_h16: grad_value too large");
-    if ((((uintptr_t)ws | (uintptr_t)gvalue) & 15) == 0)
-        hipLaunchKernelGGL((msda_h16_convert<T16, true>), dim3((unsigned)blocks), dim3(256), 0, st, ws, count, gvalue);
-    else
-        hipLaunchKernelGGL((msda_h16_convert<T16, false>), dim3((unsigned)blocks), dim3(256), 0, st, ws, count, gvalue);
-    g_last_kernels = "msda_bwd_h16_fused+msda_h16_convert";
-    return semidetr::launch_status("msda_h16_convert");
+    const bool f32 = prologue_type == SEMIDETR_ROW_F32;
+    if (dtype == SEMIDETR_H16_FP16) return f32 ? f(Type<__half>{}, Type<float>{}) : f(Type<__half>{}, Type<__half>{});
+    return f32 ? f(Type<__hip_bfloat16>{}, Type<float>{}) : f(Type<__hip_bfloat16>{}, Type<__hip_bfloat16>{});
 }
 
 }  // namespace semidetr_h16
@@ -842,13 +761,12 @@ extern "C" int semidetr_msda_fused_forward_h16(void *stream, int dtype, const vo
     const FusedArgs a = {value, spatial_shapes, level_start, reference_points, ref_dim, sampling_offsets, attn_logits, prologue_type,
                          padding_mask, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point};
     if (int rc = check_fused(a, dtype, out, "msda_fused_forward_h16")) return rc;
-    const hipStream_t st = semidetr::as_stream(stream);
-    const bool f32 = prologue_type == SEMIDETR_ROW_F32;
-    if (dtype == SEMIDETR_H16_FP16)
-        return f32 ? fused_forward_impl<__half, float>(st, a, static_cast<__half *>(out))
-                   : fused_forward_impl<__half, __half>(st, a, static_cast<__half *>(out));
-    return f32 ? fused_forward_impl<__hip_bfloat16, float>(st, a, static_cast<__hip_bfloat16 *>(out))
-               : fused_forward_impl<__hip_bfloat16, __hip_bfloat16>(st, a, static_cast<__hip_bfloat16 *>(out));
+    return with_types(dtype, prologue_type, [&](auto t16, auto pt) {
+        using T16 = typename decltype(t16)::type;
+        using PT = typename decltype(pt)::type;
+        return launch_fast_forward(semidetr::as_stream(stream), static_cast<const T16 *>(value), spatial_shapes, level_start,
+                                   a.io<PT>(nullptr, nullptr), a.dims(), static_cast<T16 *>(out), "msda_fused_forward_h16");
+    });
 }
 
 extern "C" int semidetr_msda_fused_backward_h16(void *stream, int dtype, const void *grad_out, const void *value,
@@ -870,19 +788,17 @@ extern "C" int semidetr_msda_fused_backward_h16(void *stream, int dtype, const v
                      SEMIDETR_E_BADARG,
                      "msda_fused_backward_h16: grad_value must be 2-byte, workspace and grad_attn_logits 4-byte, grad_sampling_offsets "
                      "8-byte aligned");
-    const hipStream_t st = semidetr::as_stream(stream);
-    float *ws = static_cast<float *>(workspace);
-    const bool f32 = prologue_type == SEMIDETR_ROW_F32;
-    if (dtype == SEMIDETR_H16_FP16) {
-        const __half *go = static_cast<const __half *>(grad_out);
-        __half *gv = static_cast<__half *>(grad_value);
-        return f32 ? fused_backward_impl<__half, float>(st, a, go, ws, gv, grad_sampling_offsets, grad_attn_logits)
-                   : fused_backward_impl<__half, __half>(st, a, go, ws, gv, grad_sampling_offsets, grad_attn_logits);
-    }
-    const __hip_bfloat16 *go = static_cast<const __hip_bfloat16 *>(grad_out);
-    __hip_bfloat16 *gv = static_cast<__hip_bfloat16 *>(grad_value);
-    return f32 ? fused_backward_impl<__hip_bfloat16, float>(st, a, go, ws, gv, grad_sampling_offsets, grad_attn_logits)
-               : fused_backward_impl<__hip_bfloat16, __hip_bfloat16>(st, a, go, ws, gv, grad_sampling_offsets, grad_attn_logits);
+    return with_types(dtype, prologue_type, [&](auto t16, auto pt) {
+        using T16 = typename decltype(t16)::type;
+        using PT = typename decltype(pt)::type;
+        const hipStream_t st = semidetr::as_stream(stream);
+        const RawIO16<PT> io = a.io<PT>(grad_sampling_offsets, grad_attn_logits);
+        float *ws = static_cast<float *>(workspace);
+        if (int rc = launch_fast_backward(st, static_cast<const T16 *>(grad_out), static_cast<const T16 *>(value), spatial_shapes,
+                                          level_start, io, a.dims(), ws, "msda_fused_backward_h16"))
+            return rc;
+        return convert_grad_value(st, ws, a.dims(), static_cast<T16 *>(grad_value), RawIO16<PT>::kBwd, "msda_fused_backward_h16");
+    });
 }
 
 extern "C" const char *semidetr_msda_h16_last_kernels(void) { return semidetr_h16::g_last_kernels; }
@@ -903,14 +819,12 @@ extern "C" int semidetr_msda_forward_h16(void *stream, int dtype, const void *va
                               channels, num_levels, num_query, num_point))
         return rc;
     SEMIDETR_REQUIRE(out && ((uintptr_t)out & 1) == 0, SEMIDETR_E_BADARG, "msda_forward_h16: null or odd output pointer");
-    const hipStream_t st = semidetr::as_stream(stream);
-    if (dtype == SEMIDETR_H16_FP16)
-        return forward_impl<__half>(st, static_cast<const __half *>(value), spatial_shapes, level_start, sampling_loc, attn_weight,
-                                    batch, spatial_size, num_heads, channels, num_levels, num_query, num_point,
-                                    static_cast<__half *>(out));
-    return forward_impl<__hip_bfloat16>(st, static_cast<const __hip_bfloat16 *>(value), spatial_shapes, level_start, sampling_loc,
-                                        attn_weight, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point,
-                                        static_cast<__hip_bfloat16 *>(out));
+    const Dims d = {batch, spatial_size, num_heads, channels, num_levels, num_query, num_point};
+    return with_types(dtype, SEMIDETR_ROW_F32, [&](auto t16, auto) {
+        using T16 = typename decltype(t16)::type;
+        return forward_impl(semidetr::as_stream(stream), static_cast<const T16 *>(value), spatial_shapes, level_start,
+                            LocAttnIO16{sampling_loc, attn_weight, nullptr, nullptr}, d, static_cast<T16 *>(out));
+    });
 }
 
 extern "C" int semidetr_msda_backward_h16(void *stream, int dtype, const void *grad_out, const void *value,
@@ -927,14 +841,11 @@ extern "C" int semidetr_msda_backward_h16(void *stream, int dtype, const void *g
                      "msda_backward_h16: null pointer argument");
     SEMIDETR_REQUIRE((((uintptr_t)grad_out | (uintptr_t)grad_value) & 1) == 0 && ((uintptr_t)workspace & 3) == 0, SEMIDETR_E_BADARG,
                      "msda_backward_h16: grad_out / grad_value must be 2-byte aligned, workspace 4-byte aligned");
-    const hipStream_t st = semidetr::as_stream(stream);
-    if (dtype == SEMIDETR_H16_FP16)
-        return backward_impl<__half>(st, static_cast<const __half *>(grad_out), static_cast<const __half *>(value), spatial_shapes,
-                                     level_start, sampling_loc, attn_weight, batch, spatial_size, num_heads, channels, num_levels,
-                                     num_query, num_point, static_cast<float *>(workspace), static_cast<__half *>(grad_value),
-                                     grad_sampling_loc, grad_attn_weight);
-    return backward_impl<__hip_bfloat16>(st, static_cast<const __hip_bfloat16 *>(grad_out), static_cast<const __hip_bfloat16 *>(value),
-                                         spatial_shapes, level_start, sampling_loc, attn_weight, batch, spatial_size, num_heads,
-                                         channels, num_levels, num_query, num_point, static_cast<float *>(workspace),
-                                         static_cast<__hip_bfloat16 *>(grad_value), grad_sampling_loc, grad_attn_weight);
+    const Dims d = {batch, spatial_size, num_heads, channels, num_levels, num_query, num_point};
+    return with_types(dtype, SEMIDETR_ROW_F32, [&](auto t16, auto) {
+        using T16 = typename decltype(t16)::type;
+        return backward_impl(semidetr::as_stream(stream), static_cast<const T16 *>(grad_out), static_cast<const T16 *>(value), spatial_shapes,
+                             level_start, LocAttnIO16{sampling_loc, attn_weight, grad_sampling_loc, grad_attn_weight}, d,
+                             static_cast<float *>(workspace), static_cast<T16 *>(grad_value));
+    });
 }
