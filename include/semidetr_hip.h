@@ -1231,6 +1231,76 @@ typedef struct semidetr_ref_points {
 int semidetr_ref_points_forward(void *stream, const semidetr_ref_points *params /* host */);
 int semidetr_ref_points_backward(void *stream, const semidetr_ref_points *params /* host */);
 
+/* ---------------------------------------------------------------------------------------------
+ * Pyramid inputs of the transformer (csrc/pyramid_inputs.hip): the level masks, SinePositionalEncodingHW of every level with the
+ * level_embed row added, flattened and concatenated (positional_encoding.py:57-99, transformer.py:1271-1289), mask_flatten,
+ * get_valid_ratio (:1237-1244, 1292) and the encoder's get_reference_points (:676-691) -- two launches forward for the whole
+ * pyramid and batch, two backward.  Token row `start[l] + i * w[l] + j` of image n is pixel (i, j) of level l.
+ *
+ * The level masks.  from_sizes != 0: pixel (i, j) of level l is masked iff src(i, input_h, h[l]) >= img_h[n] or
+ *   src(j, input_w, w[l]) >= img_w[n], src(d, in, out) = min((int)floorf(d * ((float)in / (float)out)), in - 1): the nearest rule
+ *   of F.interpolate on the (input_h, input_w) image mask whose top-left (img_h[n], img_w[n]) corner is valid (0 <= img_h[n] <=
+ *   input_h, likewise w).  from_sizes == 0: masks[l] holds (batch, h[l], w[l]) bytes, contiguous; non-zero = masked.
+ * Counts.  cnt_y(i, j) = valid pixels of column j in rows 0 .. i, tot_y(j) = cnt_y(h - 1, j); cnt_x / tot_x the same along the
+ *   row.  Exact integers (16-bit: h, w < 65536).
+ * pos[n, row, c], every operation rounded on its own in fp32, IEEE division, precise sinf / cosf:
+ *   normalize != 0:  y = ((cnt_y + offset) / (tot_y + eps)) * scale,  else y = cnt_y;  x likewise from cnt_x, tot_x.
+ *   c < 128:   (c even ? sinf : cosf)(y / dim_ty[c]);   c >= 128:  (c even ? sinf : cosf)(x / dim_tx[c - 128]);
+ *   + level_embed[l, c] (exactly up-cast) where level_embed != NULL; rounded once to pos_type.
+ *   dim_ty / dim_tx are the caller's tables of 128 fp32 divisors (the kernels evaluate no pow).
+ * mask_flatten[n, row] = 0 / 1 bytes.  valid_ratios[n, l] = ((float)tot_x(row 0) * (1.0f / w[l]), (float)tot_y(column 0) *
+ *   (1.0f / h[l])): the product with the fp32 reciprocal, which is what torch's division of a GPU tensor by a host number computes
+ *   (get_valid_ratio's `valid_W.float() / W`); it differs from the IEEE quotient by an ulp for some counts.
+ * reference_points[n, row, l', :] (NULL = not wanted), vr = valid_ratios[n]:
+ *   ((j + 0.5f) / (vr[l][0] * w[l])) * vr[l'][0],  ((i + 0.5f) / (vr[l][1] * h[l])) * vr[l'][1]   -- a level without a valid pixel
+ *   in row 0 or column 0 gives what IEEE gives (x / 0, inf * 0), as stock torch does.
+ *
+ * semidetr_pyramid_inputs_forward   launch 1, one 64-lane workgroup per 64 columns and one per 64 rows of an (image, level) -- a
+ *   grid of batch * (ceil(w / 64) + ceil(h / 64)) summed over the levels: a lane walks its column down (its row along), writes the
+ *   mask bytes (column walk), the running counts into the workspace and, from column 0 and row 0, the valid ratios.  Launch 2, a workgroup per 32 token rows of an
+ *   (image, level): one lane handles 4 consecutive channels of a token, a wave stores a whole row (16 bytes per lane, 8 for a
+ *   16-bit pos_type), lanes 0 .. 2 * levels - 1 the row's reference points.
+ * semidetr_pyramid_inputs_backward  grad_level_embed[l, c] = sum over n and the rows of level l of g[n, row, c]; g has g_type and
+ *   is read in place through g_stride (elements, last stride 1).  Launch 1: a workgroup adds 256 rows of an (image, level) in
+ *   fp32 in a fixed order into a slot of the workspace; launch 2 adds a level's slots in fp64 in a fixed order and rounds once
+ *   to level_embed_type.  Nothing else receives a gradient.
+ * No float atomics, no memset; every grid and order depends on the sizes alone: two runs are bitwise equal.
+ * semidetr_pyramid_inputs_workspace_bytes  the bytes either call needs (sizes only; 0 for sizes the calls refuse).
+ * Checked on the host before any launch (SEMIDETR_E_BADARG, nothing is written): levels outside 1 .. SEMIDETR_PYR_MAX_LEVELS,
+ *   batch outside 1 .. SEMIDETR_PYR_MAX_BATCH, h[l] or w[l] outside 1 .. 65535, levels whose rows overlap, are out of order or
+ *   pass tokens_per_image, an image size outside the input shape, normalize with eps <= 0 or a NaN setting, an unknown type
+ *   code, a NULL or misaligned pointer (16 bytes: pos, g, dim_ty, dim_tx, level_embed, the workspace; 8 for 16-bit pos and g), a
+ *   workspace smaller than the query says.  SEMIDETR_E_TOOLARGE: batch * tokens_per_image * 256 >= 2^31.
+ * ------------------------------------------------------------------------------------------- */
+#define SEMIDETR_PYR_MAX_LEVELS 8
+#define SEMIDETR_PYR_MAX_BATCH 64
+typedef struct semidetr_pyramid_inputs {
+    int batch, levels;
+    int h[SEMIDETR_PYR_MAX_LEVELS], w[SEMIDETR_PYR_MAX_LEVELS];
+    int64_t start[SEMIDETR_PYR_MAX_LEVELS];               /* first token row of level l */
+    int64_t tokens_per_image;
+    int from_sizes, input_h, input_w;                     /* batch_input_shape */
+    int img_h[SEMIDETR_PYR_MAX_BATCH], img_w[SEMIDETR_PYR_MAX_BATCH];     /* by value: no staging copy */
+    const void *masks[SEMIDETR_PYR_MAX_LEVELS];           /* from_sizes == 0: (batch, h[l], w[l]) bytes */
+    int normalize;
+    float offset, eps, scale;
+    const float *dim_ty, *dim_tx;                         /* 128 divisors each */
+    const void *level_embed;                              /* (levels, 256) of level_embed_type, or NULL */
+    int level_embed_type, pos_type, g_type;               /* SEMIDETR_ROW_* */
+    void *pos;                                            /* forward: written, (batch, tokens_per_image, 256) */
+    void *mask_flatten;                                   /* forward: written, (batch, tokens_per_image) bytes */
+    float *valid_ratios;                                  /* forward: written, (batch, levels, 2) */
+    float *reference_points;                              /* forward: written, (batch, tokens_per_image, levels, 2), or NULL */
+    const void *g;                                        /* backward: upstream gradient of pos */
+    int64_t g_stride[2];                                  /* in elements */
+    void *grad_level_embed;                               /* backward: written, (levels, 256) of level_embed_type */
+} semidetr_pyramid_inputs;
+size_t semidetr_pyramid_inputs_workspace_bytes(const semidetr_pyramid_inputs *params /* host */, int for_backward);
+int semidetr_pyramid_inputs_forward(void *stream, const semidetr_pyramid_inputs *params /* host */, void *workspace,
+                                    size_t workspace_bytes);
+int semidetr_pyramid_inputs_backward(void *stream, const semidetr_pyramid_inputs *params /* host */, void *workspace,
+                                     size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

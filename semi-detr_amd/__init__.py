@@ -38,6 +38,8 @@ from .input_proj import (GroupNormTokensFunction, group_norm_to_tokens, group_no
                          group_norm_tokens_forward, project_pyramid)
 from .ref_points import (RefPointsFunction, box_outputs, decoder_forward, gen_sineembed_for_position,  # noqa: E402,F401
                          reference_inputs, refine_boxes)
+from .pyramid_inputs import (PyramidInputs, PyramidInputsFunction, SinePositionalEncodingHW, head_inputs,  # noqa: E402,F401
+                             pyramid_inputs, pyramid_inputs_backward, pyramid_inputs_from_masks)
 from .pseudo_label import (filter_pseudo_labels, get_bboxes_for_pseudo_label, teacher_pseudo_labels,  # noqa: E402,F401
                            transform_bboxes)
 
@@ -54,4 +56,5 @@ __all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttnMix
            "decoder_layer_forward", "decoder_layer_forward_sa", "decoder_layer_forward_ca", "decoder_layer_forward_ffn",
            "group_norm_tokens_forward", "group_norm_tokens_backward", "GroupNormTokensFunction", "group_norm_to_tokens",
            "project_pyramid", "gen_sineembed_for_position", "refine_boxes", "reference_inputs", "decoder_forward", "box_outputs",
-           "RefPointsFunction"]
+           "RefPointsFunction", "pyramid_inputs", "pyramid_inputs_from_masks", "pyramid_inputs_backward", "PyramidInputs",
+           "PyramidInputsFunction", "SinePositionalEncodingHW", "head_inputs"]

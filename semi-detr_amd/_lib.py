@@ -170,6 +170,21 @@ class RefPoints(ctypes.Structure):
                 + _f(RefSegment * REF_MAX_SEGMENTS, "segment"))
 
 
+# the level table and the by-value image sizes of semidetr_pyramid_inputs: SEMIDETR_PYR_MAX_LEVELS levels, SEMIDETR_PYR_MAX_BATCH
+# images (tests/test_pyramid_inputs_ref.py reads the macros back from the header)
+PYR_MAX_LEVELS, PYR_MAX_BATCH = 8, 64
+_PYR_I32, _PYR_IMG = ctypes.c_int * PYR_MAX_LEVELS, ctypes.c_int * PYR_MAX_BATCH
+
+
+class PyramidInputsBlock(ctypes.Structure):
+    _fields_ = (_f(c_int, "batch levels") + _f(_PYR_I32, "h w") + _f(c_int64 * PYR_MAX_LEVELS, "start")
+                + _f(c_int64, "tokens_per_image") + _f(c_int, "from_sizes input_h input_w") + _f(_PYR_IMG, "img_h img_w")
+                + _f(c_void_p * PYR_MAX_LEVELS, "masks") + _f(c_int, "normalize") + _f(c_float, "offset eps scale")
+                + _f(c_void_p, "dim_ty dim_tx level_embed") + _f(c_int, "level_embed_type pos_type g_type")
+                + _f(c_void_p, "pos mask_flatten valid_ratios reference_points g") + _f(_STRIDE2, "g_stride")
+                + _f(c_void_p, "grad_level_embed"))
+
+
 # C struct -> mirror, in the header's order
 STRUCTS = {"semidetr_cost_params": CostParams, "semidetr_match_table": MatchTable, "semidetr_image_sizes": ImageSizes,
            "semidetr_box_table": BoxTable, "semidetr_set_loss_segment": SetLossSegment, "semidetr_dn_layout": DnLayout,
@@ -177,7 +192,7 @@ STRUCTS = {"semidetr_cost_params": CostParams, "semidetr_match_table": MatchTabl
            "semidetr_consis_loss": ConsisLoss, "semidetr_self_attn": SelfAttn, "semidetr_self_attn_h16": SelfAttnH16,
            "semidetr_add_norm": AddNorm,
            "semidetr_add_norm_mixed": AddNormMixed, "semidetr_gn_tokens": GnTokens,
-           "semidetr_ref_segment": RefSegment, "semidetr_ref_points": RefPoints}
+           "semidetr_ref_segment": RefSegment, "semidetr_ref_points": RefPoints, "semidetr_pyramid_inputs": PyramidInputsBlock}
 _SEGS, _WORK = POINTER(SetLossSegment), [c_void_p, c_size_t]        # a segment table; the (workspace, workspace_bytes) pair
 
 _MSDA_FWD = [c_void_p] * 6 + [c_int] * 7 + [c_void_p]
@@ -284,6 +299,10 @@ SIGNATURES = {
     # reference-point chain of the decoder: refine, valid-ratio scaling, sine embed (ref_points.py)
     "semidetr_ref_points_forward": (c_int, [c_void_p, POINTER(RefPoints)]),
     "semidetr_ref_points_backward": (c_int, [c_void_p, POINTER(RefPoints)]),
+    # pyramid masks, sine position rows, valid ratios and encoder reference points (pyramid_inputs.py)
+    "semidetr_pyramid_inputs_workspace_bytes": (c_size_t, [POINTER(PyramidInputsBlock), c_int]),
+    "semidetr_pyramid_inputs_forward": (c_int, [c_void_p, POINTER(PyramidInputsBlock)] + _WORK),
+    "semidetr_pyramid_inputs_backward": (c_int, [c_void_p, POINTER(PyramidInputsBlock)] + _WORK),
 }
 
 # include/semidetr_hip_experiments.h: only in libsemidetr_hip_exp.so

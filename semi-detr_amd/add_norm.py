@@ -323,17 +323,18 @@ def encoder_layer_forward_ffn(layer, src):
 
 
 def encoder_forward(encoder, src, pos, spatial_shapes, level_start_index, valid_ratios, key_padding_mask,
-                    ref_token_index=None, ref_token_coord=None, query=None):
+                    ref_token_index=None, ref_token_coord=None, query=None, reference_points=None):
     """``DINOTransformerEncoder.forward`` (transformer.py:693-744): each layer's FFN epilogue also writes ``output + pos`` for
     the next layer, so the only stand-alone ``src + pos`` pass is the one in front of layer 0.  ``query``: ``src + pos`` where
     the caller already has it (``input_proj.project_pyramid`` writes it with the tokens); layer 0 then takes it and no
-    stand-alone pass is left."""
+    stand-alone pass is left.  ``reference_points``: the ``(N, S, L, 2)`` tensor ``encoder.get_reference_points`` would return,
+    where the caller already has it (``pyramid_inputs`` writes it); the call is then not made."""
     if encoder.two_stage_type != 'standard' or encoder.deformable_encoder is not True or ref_token_index is not None \
             or ref_token_coord is not None:
         raise NotImplementedError("encoder_forward: only the standard two-stage deformable encoder without reference tokens")
     output = src
     layers = list(encoder.layers)
-    if layers:
+    if layers and reference_points is None:
         reference_points = encoder.get_reference_points(spatial_shapes, valid_ratios, device=src.device)
     for i, layer in enumerate(layers):
         more = i + 1 < len(layers)

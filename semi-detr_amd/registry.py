@@ -9,7 +9,7 @@ they exist; importing it elsewhere is harmless (returns the list of names it cou
 """
 
 
-def register_all(force=True):
+def register_all(force=True, positional_encoding=None):
     from .matcher import BBoxL1Cost, FocalLossCost, HungarianAssigner, IoUCost, O2MAssigner
     from .mean_teacher import MeanTeacher
 
@@ -44,6 +44,17 @@ def register_all(force=True):
         done.append("FlatDDP")
     except ImportError:
         skipped.append("FlatDDP")
+    # the pyramid's positional encoding under the reference's name (positional_encoding.py:9), where a registry is given or
+    # mmcv's is importable; without either there is nothing to report
+    if positional_encoding is None:
+        try:
+            from mmcv.cnn.bricks.transformer import POSITIONAL_ENCODING as positional_encoding
+        except ImportError:
+            positional_encoding = None
+    if positional_encoding is not None:
+        from .pyramid_inputs import SinePositionalEncodingHW
+        positional_encoding.register_module(name="SinePositionalEncodingHW", force=force, module=SinePositionalEncodingHW)
+        done.append("SinePositionalEncodingHW")
     return done, skipped
 
 
