@@ -85,6 +85,32 @@ const char *semidetr_last_error(void);
  * SEMIDETR_MSDA_FIXED_FORWARD still wins (patch gather). */
 #define SEMIDETR_MSDA_GATHER_WINDOW (1 << 16)
 #define SEMIDETR_MSDA_GATHER_PATCH (1 << 17)
+/* The paragraph above stays true of every entry point declared before this one.  The EXACT backward (additive, ABI 7; fp32,
+ * channels == 32) is the opt-in exception: semidetr_msda_backward_exact_f32 takes the arguments of semidetr_msda_backward_f32 plus a
+ * workspace and returns
+ *   grad_value[n, row, m, d] = the EXACT sum of its fp32 contributions, rounded once to nearest even,
+ * where, for a valid corner k of a sample with attention weight a, w = fl(a * c_k) with c_k the fp32 product of the corner's two
+ * bilinear factors, and contribution[d] = fl(w * grad_out[n, q, m, d]) (each a single individually rounded operation).  The bits of
+ * grad_value are therefore a function of the SET of contributions: the same on every run, for every launch order, independent of the
+ * image's position in the batch, of the order in which queries or points are listed and of `flags`.  A sum that exceeds fp32's range
+ * is +-inf exactly when the exact sum rounds there; non-finite contributions give what IEEE addition gives in every order (NaN if a
+ * NaN or both infinities occur, otherwise the infinity).  Every element of grad_value is written exactly once (rows nobody samples
+ * are stored as zeros): the buffer needs no fill.  No float atomic is used: contributions are counted and bucketed per destination
+ * row with integer atomics into the workspace (8 bytes per (query, head, level, point, corner)), then each row is summed in a long
+ * fixed-point accumulator.  grad_sampling_loc / grad_attn_weight come from the gather kernels of the default route, which never used
+ * atomics (with SEMIDETR_MSDA_QUERIES_ARE_PIXELS: the patch gather, as under SEMIDETR_MSDA_FIXED_FORWARD); all three results are
+ * bitwise reproducible.  The price is time: the route is for runs that must be reproducible, not for speed.
+ *   workspace: device memory, 16-byte aligned, at least semidetr_msda_exact_workspace_bytes(...) bytes (0: the sizes are not
+ *   supported); contents need no initialisation and mean nothing afterwards.  No host synchronisation, no allocation: legal inside a
+ *   stream capture.  SEMIDETR_E_BADARG (reason in semidetr_last_error) for channels != 32, num_levels * num_point > 62 (the gather
+ *   kernel's LDS), more than 32 heads, pointers not 16-byte aligned, a workspace too small or misaligned, and
+ *   num_query * num_levels * num_point * 4 >= 2^32.  Bits 8..17 of `flags` are accepted and ignored. */
+size_t semidetr_msda_exact_workspace_bytes(int batch, int spatial_size, int num_heads, int num_levels, int num_query, int num_point);
+int semidetr_msda_backward_exact_f32(void *stream, const float *grad_out, const float *value, const int64_t *spatial_shapes,
+                                     const int64_t *level_start, const float *sampling_loc, const float *attn_weight, int batch,
+                                     int spatial_size, int num_heads, int channels, int num_levels, int num_query, int num_point,
+                                     int flags, void *workspace, size_t workspace_bytes, float *grad_value,
+                                     float *grad_sampling_loc, float *grad_attn_weight);
 int semidetr_msda_forward_f32(void *stream, const float *value, const int64_t *spatial_shapes,
                               const int64_t *level_start, const float *sampling_loc,
                               const float *attn_weight, int batch, int spatial_size, int num_heads,

@@ -21,6 +21,12 @@ re-exports its functions; there is no Python or CPU implementation to fall back 
     ms_deform_attn_h16_fused_backward(..., attn_logits, grad_output16[, padding_mask])
                                 -> [grad_value (value's dtype), grad_sampling_offsets, grad_attn_logits (the offsets' dtype)]
     fused_h16_supported(value, reference_points, sampling_offsets, attn_logits) -> the fused 16-bit kernels take these tensors
+    ms_deform_attn_exact_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step) -> Tensor
+                                the fp32 forward whose kernel is a function of the arguments alone (SEMIDETR_MSDA_FIXED_FORWARD)
+    ms_deform_attn_exact_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step)
+                                -> [grad_value, grad_sampling_loc, grad_attn_weight]: grad_value is the exact sum of its fp32
+                                contributions rounded once -- bitwise independent of order (fp32, 32 channels)
+    exact_supported(value, num_levels, num_point) -> the exact backward takes this value map (after an up-cast if it is 16-bit)
     pyramid_check(spatial_shapes, level_start_index, S) -> bit 0: sum(H*W) == S, bit 1: exact tiling (cached)
     mask_extents(padding_mask, spatial_shapes, level_start_index) -> (N, L) int32 summary of a padding mask (cached; the
                                                                       fused calls fetch it themselves)
@@ -51,6 +57,9 @@ h16_supported = _msda_ext.h16_supported
 ms_deform_attn_h16_fused_forward = _msda_ext.ms_deform_attn_h16_fused_forward
 ms_deform_attn_h16_fused_backward = _msda_ext.ms_deform_attn_h16_fused_backward
 fused_h16_supported = _msda_ext.fused_h16_supported
+ms_deform_attn_exact_forward = _msda_ext.ms_deform_attn_exact_forward
+ms_deform_attn_exact_backward = _msda_ext.ms_deform_attn_exact_backward
+exact_supported = _msda_ext.exact_supported
 pyramid_check = _msda_ext.pyramid_check
 mask_extents = _msda_ext.mask_extents
 gather_choice = _msda_ext.gather_choice

@@ -15,8 +15,9 @@ from . import MultiScaleDeformableAttention as _msda_native
 # (detr_od/models/utils/ops/functions/ms_deform_attn_func.py:18); make that import resolve to ours.
 _sys.modules.setdefault("MultiScaleDeformableAttention", _msda_native)
 
-from .ops.functions import MSDeformAttnFunction, MSDeformAttnFusedFunction, MSDeformAttnMixedFunction, MSDeformAttnMixedFusedFunction  # noqa: E402,F401
-from .ops.modules import MSDeformAttn  # noqa: E402,F401
+from .ops.functions import (MSDeformAttnExactFunction, MSDeformAttnFunction, MSDeformAttnFusedFunction,  # noqa: E402,F401
+                            MSDeformAttnMixedFunction, MSDeformAttnMixedFusedFunction)
+from .ops.modules import MSDeformAttn, convert_exact_backward  # noqa: E402,F401
 from .matcher import (AssignResult, BBoxL1Cost, FocalLossCost, HungarianAssigner, IoUCost,  # noqa: E402,F401
                       O2MAssigner, O2MAssignResult, linear_sum_assignment)
 from .losses import TaskAlignedFocalLoss, task_aligned_focal_loss  # noqa: E402,F401
@@ -43,7 +44,7 @@ from .pyramid_inputs import (PyramidInputs, PyramidInputsFunction, SinePositiona
 from .pseudo_label import (filter_pseudo_labels, get_bboxes_for_pseudo_label, teacher_pseudo_labels,  # noqa: E402,F401
                            transform_bboxes)
 
-__all__ = ["MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttnMixedFunction", "MSDeformAttnMixedFusedFunction", "MSDeformAttn", "HungarianAssigner", "FocalLossCost", "BBoxL1Cost",
+__all__ = ["MSDeformAttnExactFunction", "convert_exact_backward", "MSDeformAttnFunction", "MSDeformAttnFusedFunction", "MSDeformAttnMixedFunction", "MSDeformAttnMixedFusedFunction", "MSDeformAttn", "HungarianAssigner", "FocalLossCost", "BBoxL1Cost",
            "IoUCost", "AssignResult", "O2MAssigner", "O2MAssignResult", "TaskAlignedFocalLoss", "task_aligned_focal_loss", "linear_sum_assignment", "MeanTeacher", "ema_momentum", "ema_update_",
            "ema_update_flat_", "filter_pseudo_labels", "get_bboxes_for_pseudo_label", "teacher_pseudo_labels",
            "transform_bboxes", "TargetAssigner", "get_targets", "get_targets_layers", "fit_gmm", "fit_gmm_threshold",

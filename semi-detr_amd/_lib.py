@@ -216,6 +216,9 @@ SIGNATURES = {
     "semidetr_msda_fused_forward_f32_v2": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 4 + [c_int] * 8 + [c_void_p] * 2),
     "semidetr_msda_fused_backward_f32_v2": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 4 + [c_int] * 8 + [c_void_p] * 4),
     "semidetr_msda_mask_extents": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
+    # the exact backward: the arguments of semidetr_msda_backward_f32 with the (workspace, workspace_bytes) pair before the results
+    "semidetr_msda_exact_workspace_bytes": (c_size_t, [c_int] * 6),
+    "semidetr_msda_backward_exact_f32": (c_int, [c_void_p] * 7 + [c_int] * 8 + _WORK + [c_void_p] * 3),
     "semidetr_msda_last_kernels": (ctypes.c_char_p, []),
     "semidetr_msda_forward_h16": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
     "semidetr_msda_backward_h16_workspace_bytes": (c_size_t, [c_int] * 4),

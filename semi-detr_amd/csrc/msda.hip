@@ -231,6 +231,7 @@ int backward_impl(void *stream, const T *gout, const T *value, const int64_t *sh
 #include "msda_grid.h"       // region-grid chooser of the encoder window kernels: plain C++, also built alone by tests/host/msda_grid_host_check.cpp
 #include "msda_policy.h"     // data-driven choice between the patch and the window kernels, per (device, call-site slot)
 #include "msda_dispatch.h"   // RwProduct / GwProduct / ScatterProduct, the grid hints, launch_fast_forward / launch_fast_backward
+#include "msda_exact.h"      // namespace semidetr_exact: the exact (order-independent) grad_value pipeline of semidetr_msda_backward_exact_f32
 #if SEMIDETR_EXPERIMENTS
 namespace {
 #include "msda_experiments.h"
@@ -415,6 +416,98 @@ extern "C" int semidetr_msda_backward_f32(void *stream, const float *grad_out, c
     return semidetr_msda_backward_f32_v2(stream, grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, batch,
                                          spatial_size, num_heads, channels, num_levels, num_query, num_point, flags, grad_value,
                                          grad_sampling_loc, grad_attn_weight, nullptr);
+}
+
+// ---- exact backward (opt-in): grad_value as the exact sum of its contributions, rounded once (msda_exact.h) ------------
+// entries per (image, head) = num_query * num_levels * num_point * 4, or 0 when that is not below 2^32
+static uint64_t exact_slice_entries(int L, int Lq, int P)
+{
+    uint64_t e = (uint64_t)Lq * (uint64_t)L;
+    if (e >= (1ull << 32)) return 0;
+    e *= (uint64_t)P;
+    if (e >= (1ull << 30)) return 0;
+    return e * 4;
+}
+
+extern "C" size_t semidetr_msda_exact_workspace_bytes(int batch, int spatial_size, int num_heads, int num_levels, int num_query,
+                                                      int num_point)
+{
+    if (batch <= 0 || spatial_size <= 0 || num_heads <= 0 || num_levels <= 0 || num_query <= 0 || num_point <= 0) return 0;
+    if (!exact_slice_entries(num_levels, num_query, num_point)) return 0;
+    return semidetr_exact::workspace_layout(batch, spatial_size, num_heads, num_levels, num_query, num_point).total_bytes;
+}
+
+extern "C" int semidetr_msda_backward_exact_f32(void *stream, const float *grad_out, const float *value, const int64_t *spatial_shapes,
+                                                const int64_t *level_start, const float *sampling_loc, const float *attn_weight,
+                                                int batch, int spatial_size, int num_heads, int channels, int num_levels,
+                                                int num_query, int num_point, int flags, void *workspace, size_t workspace_bytes,
+                                                float *grad_value, float *grad_sampling_loc, float *grad_attn_weight)
+{
+    namespace ex = semidetr_exact;
+    const int N = batch, S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query, P = num_point;
+    if (int rc = check_common(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P, 4)) return rc;
+    SEMIDETR_REQUIRE(grad_out && grad_value && grad_sampling_loc && grad_attn_weight && workspace, SEMIDETR_E_BADARG,
+                     "msda_backward_exact: null pointer argument");
+    SEMIDETR_REQUIRE(D == kD, SEMIDETR_E_BADARG, "msda_backward_exact: channels must be 32 (got %d)", D);
+    // (the small gradients come from the strips / patch gather: 32 rows of L * P + 1 records and the level table in 64 KB of LDS)
+    const size_t glds = (size_t)32 * ((size_t)L * P + 1) * 32 + 2 * kMaxLevels * sizeof(float);
+    SEMIDETR_REQUIRE(L <= kMaxLevels && (int64_t)L * P <= 256 && glds <= 64 * 1024, SEMIDETR_E_BADARG,
+                     "msda_backward_exact: num_levels * num_point = %lld does not fit the gather kernel's LDS (at most 62, <= %d levels)",
+                     (long long)L * P, kMaxLevels);
+    SEMIDETR_REQUIRE(heads_ok(M) && slice_ok(S, M), SEMIDETR_E_BADARG, "msda_backward_exact: <= 32 heads, image slice < 4 GB");
+    SEMIDETR_REQUIRE(fast_ok(value, sampling_loc, grad_out, D, L, P) && fast_ok(grad_value, grad_sampling_loc, grad_attn_weight, D, L, P) &&
+                         (reinterpret_cast<uintptr_t>(attn_weight) & 15) == 0,
+                     SEMIDETR_E_BADARG, "msda_backward_exact: pointers must be 16-byte aligned");
+    const uint64_t slice = exact_slice_entries(L, Lq, P);
+    SEMIDETR_REQUIRE(slice != 0, SEMIDETR_E_BADARG,
+                     "msda_backward_exact: num_query * num_levels * num_point * 4 must be below 2^32 (num_query=%d num_levels=%d num_point=%d)",
+                     Lq, L, P);
+    const ex::Workspace ws = ex::workspace_layout(N, S, M, L, Lq, P);
+    SEMIDETR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SEMIDETR_E_BADARG,
+                     "msda_backward_exact: workspace must be 16-byte aligned");
+    SEMIDETR_REQUIRE(workspace_bytes >= ws.total_bytes, SEMIDETR_E_BADARG,
+                     "msda_backward_exact: workspace too small (%zu bytes, semidetr_msda_exact_workspace_bytes says %zu)", workspace_bytes,
+                     ws.total_bytes);
+    const bool pixels = (flags & SEMIDETR_MSDA_QUERIES_ARE_PIXELS) != 0;
+    SEMIDETR_REQUIRE(!pixels || Lq == S, SEMIDETR_E_BADARG,
+                     "msda_backward_exact: SEMIDETR_MSDA_QUERIES_ARE_PIXELS needs num_query == spatial_size");
+    const int64_t samples = (int64_t)N * Lq * M * L * P, sample_blocks = (samples + 255) / 256;
+    const int tiles = (S + ex::kReduceGroups - 1) / ex::kReduceGroups;
+    const int gbound = patch_grid_hint(S, L, 32), gt = (Lq + 31) / 32;
+    SEMIDETR_REQUIRE(sample_blocks < INT32_MAX && (int64_t)N * M * tiles < INT32_MAX && (int64_t)N * std::max(gbound, gt) * M < INT32_MAX,
+                     SEMIDETR_E_TOOLARGE, "msda_backward_exact: grid too large");
+    hipStream_t st = semidetr::as_stream(stream);
+    // grad_sampling_loc / grad_attn_weight: the gather of the default route (no atomics, bitwise reproducible), zero = nullptr:
+    // the patch instantiations for encoder self-attention as launch_encoder_backward takes them, else the strips one
+    const LocAttnIO io = {sampling_loc, attn_weight, grad_sampling_loc, grad_attn_weight};
+    const bool patch = pixels && P == kPT && (L * P == 16 || L * P == 20);
+    if (patch && L * P == 16)
+        hipLaunchKernelGGL((msda_bwd_gather_d32<LocAttnIO, 16, patch_hw(4, 8), SEMIDETR_GATHER_WPE, SEMIDETR_GATHER_KB>),
+                           dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds, st, grad_out, value, spatial_shapes, level_start, io, S, M,
+                           L, Lq, P, gbound, (float4 *)nullptr, (int64_t)0);
+    else if (patch)
+        hipLaunchKernelGGL((msda_bwd_gather_d32<LocAttnIO, 20, patch_hw(4, 8), SEMIDETR_GATHER5_WPE, SEMIDETR_GATHER5_KB>),
+                           dim3((unsigned)((int64_t)N * gbound * M)), dim3(256), glds, st, grad_out, value, spatial_shapes, level_start, io, S, M,
+                           L, Lq, P, gbound, (float4 *)nullptr, (int64_t)0);
+    else
+        hipLaunchKernelGGL((msda_bwd_gather_d32<LocAttnIO, 0>), dim3((unsigned)((int64_t)N * gt * M)), dim3(256), glds, st, grad_out, value,
+                           spatial_shapes, level_start, io, S, M, L, Lq, P, gt);
+    if (int rc = semidetr::launch_status("msda_bwd_gather_d32")) return rc;
+    unsigned *count = static_cast<unsigned *>(workspace);
+    unsigned *start = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + ws.counts_bytes);
+    ex::Entry *entries = reinterpret_cast<ex::Entry *>(static_cast<char *>(workspace) + 2 * ws.counts_bytes);
+    const int64_t n16 = (int64_t)(ws.counts_bytes / 16);
+    hipLaunchKernelGGL(ex::exact_clear, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, 2048)), dim3(256), 0, st,
+                       reinterpret_cast<uint4 *>(count), n16);
+    hipLaunchKernelGGL(ex::exact_count, dim3((unsigned)sample_blocks), dim3(256), 0, st, spatial_shapes, level_start, sampling_loc, S, M, L,
+                       Lq, P, samples, count);
+    hipLaunchKernelGGL(ex::exact_scan, dim3((unsigned)(N * M)), dim3(ex::kScanThreads), 0, st, count, start, S);
+    hipLaunchKernelGGL(ex::exact_fill, dim3((unsigned)sample_blocks), dim3(256), 0, st, spatial_shapes, level_start, sampling_loc,
+                       attn_weight, S, M, L, Lq, P, samples, start, count, entries, (unsigned)slice);
+    hipLaunchKernelGGL(ex::exact_reduce, dim3((unsigned)((int64_t)N * M * tiles)), dim3(ex::kReduceThreads), 0, st, grad_out, start, count,
+                       entries, (unsigned)slice, S, M, tiles, grad_value);
+    g_last_kernels = ex::kLaunchedKernels;
+    return semidetr::launch_status("msda_backward_exact");
 }
 
 // ---- fused MSDeformAttn prologue / epilogue (fp32, channels == 32) --------------------------------------

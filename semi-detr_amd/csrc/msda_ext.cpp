@@ -178,9 +178,10 @@ int self_attention_flags(const at::Tensor &shapes, const at::Tensor &starts, int
 
 void *stream_of(const at::Tensor &t) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream(); }
 
-at::Tensor ms_deform_attn_forward(const at::Tensor &value, const at::Tensor &spatial_shapes,
-                                  const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
-                                  const at::Tensor &attn_weight, int64_t im2col_step, int64_t policy_slot)
+// extra_flags: OR-ed into the f32 call's flags (the exact route's forward: SEMIDETR_MSDA_FIXED_FORWARD whatever torch's switch says)
+at::Tensor forward_with_flags(const at::Tensor &value, const at::Tensor &spatial_shapes,
+                              const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
+                              const at::Tensor &attn_weight, int64_t im2col_step, int64_t policy_slot, int extra_flags)
 {
     const Dims d = op_dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step,
                            "ms_deform_attn_forward_cuda");
@@ -195,13 +196,72 @@ at::Tensor ms_deform_attn_forward(const at::Tensor &value, const at::Tensor &spa
                                        out.data_ptr<double>());
     else {
         HostTable ht;
-        const int flags = self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot, &ht);
+        const int flags = self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot, &ht) | extra_flags;
         rc = semidetr_msda_forward_f32_v2(stream_of(value), value.data_ptr<float>(), sh, ls, sampling_loc.data_ptr<float>(),
                                           attn_weight.data_ptr<float>(), d.N, d.S, d.M, d.D, d.L, d.Lq, d.P, flags,
                                           out.data_ptr<float>(), ht.ptr());
     }
     check_rc(rc, "ms_deform_attn_forward");
     return out;
+}
+
+at::Tensor ms_deform_attn_forward(const at::Tensor &value, const at::Tensor &spatial_shapes,
+                                  const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
+                                  const at::Tensor &attn_weight, int64_t im2col_step, int64_t policy_slot)
+{
+    return forward_with_flags(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step, policy_slot, 0);
+}
+
+// ---- the exact route (not part of the reference's pybind surface; include/semidetr_hip.h: semidetr_msda_backward_exact_f32) ----
+// what the C entry takes, so that a caller can route a call it would refuse elsewhere: fp32 / 16-bit value (the module up-casts a
+// 16-bit one first) with 32 channels per head, <= 32 heads, num_levels * num_point <= 62
+bool exact_supported(const at::Tensor &value, int64_t num_levels, int64_t num_point)
+{
+    return value.is_cuda() && value.dim() == 4 && value.size(3) == 32 && value.size(2) <= 32 && num_levels >= 1 && num_levels <= 32 &&
+           num_point >= 1 && num_levels * num_point <= 62 &&
+           (value.scalar_type() == at::kFloat || value.scalar_type() == at::kHalf || value.scalar_type() == at::kBFloat16) &&
+           value.size(1) * value.size(2) * 128 < (int64_t)0xFFFFF000u &&
+           semidetr_msda_exact_workspace_bytes(1, 1, 1, (int)num_levels, 1, (int)num_point) != 0;
+}
+
+// the forward whose kernel is a function of the arguments alone (SEMIDETR_MSDA_FIXED_FORWARD: the patch / strips kernel)
+at::Tensor ms_deform_attn_exact_forward(const at::Tensor &value, const at::Tensor &spatial_shapes,
+                                        const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
+                                        const at::Tensor &attn_weight, int64_t im2col_step, int64_t policy_slot)
+{
+    TORCH_CHECK(value.scalar_type() == at::kFloat, "ms_deform_attn_exact_forward: fp32 only, got '", scalar_name(value.scalar_type()), "'");
+    return forward_with_flags(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step, policy_slot,
+                              SEMIDETR_MSDA_FIXED_FORWARD);
+}
+
+// grad_value as the exact sum of its contributions, rounded once; the two small gradients from the atomics-free gather
+std::vector<at::Tensor> ms_deform_attn_exact_backward(const at::Tensor &value, const at::Tensor &spatial_shapes,
+                                                      const at::Tensor &level_start_index, const at::Tensor &sampling_loc,
+                                                      const at::Tensor &attn_weight, const at::Tensor &grad_output,
+                                                      int64_t im2col_step, int64_t policy_slot)
+{
+    const Dims d = op_dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step,
+                           "ms_deform_attn_exact_backward");
+    TORCH_CHECK(value.scalar_type() == at::kFloat, "ms_deform_attn_exact_backward: fp32 only, got '", scalar_name(value.scalar_type()), "'");
+    check_tensor(grad_output, value, "grad_output");
+    TORCH_CHECK(grad_output.scalar_type() == value.scalar_type() && grad_output.numel() == (int64_t)d.N * d.Lq * d.M * d.D,
+                "ms_deform_attn_exact_backward: grad_output must be (N, Lq, M*D) of value's dtype");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
+    at::Tensor gv = at::empty_like(value);            // every element is written by the reduce kernel: no fill
+    at::Tensor gl = at::empty_like(sampling_loc);
+    at::Tensor ga = at::empty_like(attn_weight);
+    if (value.numel() == 0 || gl.numel() == 0) return {gv.zero_(), gl.zero_(), ga.zero_()};
+    const size_t bytes = semidetr_msda_exact_workspace_bytes(d.N, d.S, d.M, d.L, d.Lq, d.P);
+    TORCH_CHECK(bytes != 0, "ms_deform_attn_exact_backward: num_query * num_levels * num_point * 4 must be below 2^32");
+    at::Tensor work = at::empty({(int64_t)bytes}, value.options().dtype(at::kByte));
+    const int flags = self_attention_flags(spatial_shapes, level_start_index, d.Lq, d.S, policy_slot);
+    const int rc = semidetr_msda_backward_exact_f32(stream_of(value), grad_output.data_ptr<float>(), value.data_ptr<float>(),
+                                                    spatial_shapes.data_ptr<int64_t>(), level_start_index.data_ptr<int64_t>(),
+                                                    sampling_loc.data_ptr<float>(), attn_weight.data_ptr<float>(), d.N, d.S, d.M, d.D, d.L,
+                                                    d.Lq, d.P, flags, work.data_ptr(), bytes, gv.data_ptr<float>(), gl.data_ptr<float>(),
+                                                    ga.data_ptr<float>());
+    check_rc(rc, "ms_deform_attn_exact_backward");
+    return {gv, gl, ga};
 }
 
 std::vector<at::Tensor> ms_deform_attn_backward(const at::Tensor &value, const at::Tensor &spatial_shapes,
@@ -643,6 +703,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("level_start_index"), py::arg("sampling_loc"), py::arg("attn_weight"), py::arg("grad_output"), py::arg("im2col_step"),
           py::arg("policy_slot") = 0);
     // additions
+    m.def("ms_deform_attn_exact_forward", &ms_deform_attn_exact_forward, py::arg("value"), py::arg("spatial_shapes"),
+          py::arg("level_start_index"), py::arg("sampling_loc"), py::arg("attn_weight"), py::arg("im2col_step"), py::arg("policy_slot") = 0,
+          "ms_deform_attn_forward with SEMIDETR_MSDA_FIXED_FORWARD semantics: the kernel is a function of the arguments alone");
+    m.def("ms_deform_attn_exact_backward", &ms_deform_attn_exact_backward, py::arg("value"), py::arg("spatial_shapes"),
+          py::arg("level_start_index"), py::arg("sampling_loc"), py::arg("attn_weight"), py::arg("grad_output"), py::arg("im2col_step"),
+          py::arg("policy_slot") = 0, "backward with grad_value as the exact, order-independent sum of its contributions (fp32, D = 32)");
+    m.def("exact_supported", &exact_supported, py::arg("value"), py::arg("num_levels"), py::arg("num_point"));
     m.def("ms_deform_attn_fused_forward", &ms_deform_attn_fused_forward, py::arg("value"), py::arg("spatial_shapes"),
           py::arg("level_start_index"), py::arg("reference_points"), py::arg("sampling_offsets"), py::arg("attn_logits"),
           py::arg("padding_mask") = py::none(), py::arg("policy_slot") = 0);

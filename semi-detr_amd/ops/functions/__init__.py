@@ -1,1 +1,2 @@
-from .ms_deform_attn_func import MSDeformAttnFunction, MSDeformAttnFusedFunction, MSDeformAttnMixedFunction, MSDeformAttnMixedFusedFunction  # noqa: F401
+from .ms_deform_attn_func import (MSDeformAttnExactFunction, MSDeformAttnFunction, MSDeformAttnFusedFunction,  # noqa: F401
+                                  MSDeformAttnMixedFunction, MSDeformAttnMixedFusedFunction)

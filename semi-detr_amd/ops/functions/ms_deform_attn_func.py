@@ -40,6 +40,34 @@ class MSDeformAttnFunction(Function):
         return (grad_value, None, None, grad_sampling_loc, grad_attn_weight, None, None)[:len(ctx.needs_input_grad)]
 
 
+class MSDeformAttnExactFunction(Function):
+    """``MSDeformAttnFunction`` for runs that must be reproducible bit for bit: the same ``apply`` signature (fp32, 32 channels per
+    head).  The forward is the op's forward with SEMIDETR_MSDA_FIXED_FORWARD semantics (the patch / strips kernel, whatever earlier
+    launches counted); the backward is semidetr_msda_backward_exact_f32 -- ``grad_value`` is the exact sum of its fp32 contributions
+    rounded once, so its bits do not depend on scheduling, batch position or the order of queries and points, and the two small
+    gradients come from the atomics-free gather (include/semidetr_hip.h).  Slower than the default backward."""
+
+    @staticmethod
+    def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,
+                attention_weights, im2col_step, policy_slot=0):
+        ctx.im2col_step = im2col_step
+        ctx.policy_slot = policy_slot
+        output = MSDA.ms_deform_attn_exact_forward(value, value_spatial_shapes, value_level_start_index,
+                                                   sampling_locations, attention_weights, ctx.im2col_step, policy_slot)
+        ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index, sampling_locations,
+                              attention_weights)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        value, spatial_shapes, level_start_index, sampling_locations, attention_weights = ctx.saved_tensors
+        grad_value, grad_sampling_loc, grad_attn_weight = MSDA.ms_deform_attn_exact_backward(
+            value, spatial_shapes, level_start_index, sampling_locations, attention_weights,
+            grad_output.contiguous(), ctx.im2col_step, ctx.policy_slot)
+        return (grad_value, None, None, grad_sampling_loc, grad_attn_weight, None, None)[:len(ctx.needs_input_grad)]
+
+
 class MSDeformAttnMixedFunction(Function):
     """The operator on a 16-bit value map (torch.autocast, or an all-fp16 module): ``apply(value16, value_spatial_shapes,
     value_level_start_index, sampling_locations_f32, attention_weights_f32, im2col_step)``.  ``value16`` is fp16 or bf16 and so are

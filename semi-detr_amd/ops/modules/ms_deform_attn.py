@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ... import MultiScaleDeformableAttention as MSDA
-from ..functions import (MSDeformAttnFunction, MSDeformAttnFusedFunction, MSDeformAttnMixedFunction,
+from ..functions import (MSDeformAttnExactFunction, MSDeformAttnFunction, MSDeformAttnFusedFunction, MSDeformAttnMixedFunction,
                          MSDeformAttnMixedFusedFunction)
 
 
@@ -75,6 +75,12 @@ class MSDeformAttn(nn.Module):
         # fp32, none of the fp32 (N,Lq,M,L,P[,2]) intermediates in HBM.  Off by default: the results differ from
         # torch's autocast sequence, which forms offsets / normalizer in 16 bits (here that product is fp32).  Plain attribute.
         self.fuse_prologue_16bit = False
+        # Opt-in: grad_value of this module's backward as the exact, order-independent sum of its fp32 contributions (DESIGN.md
+        # 2.12c) -- with it a training step is reproducible bit for bit through MSDA.  False: nothing changes.  True: every call a
+        # backward follows takes the op-by-op prologue and MSDeformAttnExactFunction (a 16-bit value through the up-cast route);
+        # "auto": that while torch.are_deterministic_algorithms_enabled().  A no-grad call, and a call the exact entry does not
+        # take (channels per head != 32, fp64), do exactly what they do with False.  Plain attribute, not in state_dict.
+        self.exact_backward = False
         # Which of the two encoder forward kernels runs follows how far THIS instance's learned offsets reach (semidetr_hip.h:
         # SEMIDETR_MSDA_POLICY_SLOT): instances take consecutive slots 1..255 (the reference builds 12 per model,
         # transformer.py:609,760; beyond 255 instances slots are shared, which only mixes their counts).  Plain attribute.
@@ -96,6 +102,7 @@ class MSDeformAttn(nn.Module):
         self.__dict__.setdefault("fuse_prologue", True)
         self.__dict__.setdefault("native_16bit", True)
         self.__dict__.setdefault("fuse_prologue_16bit", False)
+        self.__dict__.setdefault("exact_backward", False)
 
     def _reset_parameters(self):
         # ms_deform_attn.py:62-76 -- head m looks along direction 2*pi*m/M, point i at distance i+1
@@ -128,6 +135,19 @@ class MSDeformAttn(nn.Module):
         pixels = Len_q == Len_in and bool(MSDA.pyramid_check(shapes, starts, Len_in) & 2)
         return not _h16_takes_upcast_route(pixels, N * Len_q, follows)
 
+    def _takes_exact_route(self, value, reference_points, offsets, logits):
+        """exact_backward resolved for this call: the mode says so, a backward follows and the exact entry takes the shapes."""
+        mode = getattr(self, "exact_backward", False)
+        if mode == "auto":
+            mode = torch.are_deterministic_algorithms_enabled()
+        elif mode not in (True, False):
+            raise ValueError("MSDeformAttn.exact_backward must be False, True or 'auto', got {!r}".format(mode))
+        if not mode or not torch.is_grad_enabled():
+            return False
+        if not (value.requires_grad or offsets.requires_grad or logits.requires_grad or reference_points.requires_grad):
+            return False
+        return MSDA.exact_supported(value, self.n_levels, self.n_points)
+
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
                 input_padding_mask=None):
         """query (N, Lq, C); reference_points (N, Lq, L, 2|4) in [0,1]; input_flatten (N, sum HW, C);
@@ -148,7 +168,10 @@ class MSDeformAttn(nn.Module):
         if reference_points.shape[-1] not in (2, 4):
             raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead."
                              .format(reference_points.shape[-1]))
-        if self.fuse_prologue and MSDA.fused_supported(value, reference_points, offsets, logits):
+        exact = self._takes_exact_route(value, reference_points, offsets, logits)
+        if exact:
+            pass      # the op-by-op prologue below (torch's softmax and elementwise backward are reproducible), then the exact op
+        elif self.fuse_prologue and MSDA.fused_supported(value, reference_points, offsets, logits):
             # the padding mask (ms_deform_attn.py:95-96) goes INTO the kernels: no masked copy of `value`, no masking of its
             # gradient
             output = MSDeformAttnFusedFunction.apply(value.contiguous(), input_spatial_shapes,
@@ -156,7 +179,7 @@ class MSDeformAttn(nn.Module):
                                                      offsets.contiguous(), logits.contiguous(), input_padding_mask,
                                                      getattr(self, "policy_slot", 0))
             return self.output_proj(output)
-        if self._takes_fused_16bit_route(value, reference_points, offsets, logits, input_spatial_shapes, input_level_start_index):
+        elif self._takes_fused_16bit_route(value, reference_points, offsets, logits, input_spatial_shapes, input_level_start_index):
             output = MSDeformAttnMixedFusedFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index,
                                                           reference_points.contiguous(), offsets.contiguous(), logits.contiguous(),
                                                           input_padding_mask)
@@ -174,6 +197,11 @@ class MSDeformAttn(nn.Module):
             raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead."
                              .format(reference_points.shape[-1]))
 
+        if exact:      # fp32, or a 16-bit value up-cast as on the up-cast route below
+            output = MSDeformAttnExactFunction.apply(value.float().contiguous(), input_spatial_shapes, input_level_start_index,
+                                                     locations.float().contiguous(), weights.float().contiguous(), self.im2col_step,
+                                                     getattr(self, "policy_slot", 0))
+            return self.output_proj(output.to(value.dtype))
         if value.dtype in (torch.float16, torch.bfloat16):      # amp (ms_deform_attn.py:114-120)
             # Locations and weights are formed exactly as before and go in as fp32 (they already are under autocast; an all-fp16
             # module up-casts them as before); value goes in as it is and the op's output goes to output_proj in value's dtype.
@@ -194,3 +222,16 @@ class MSDeformAttn(nn.Module):
         output = MSDeformAttnFunction.apply(value.contiguous(), input_spatial_shapes, input_level_start_index,
                                             locations.contiguous(), weights.contiguous(), self.im2col_step, getattr(self, "policy_slot", 0))
         return self.output_proj(output)
+
+
+def convert_exact_backward(model, mode=True):
+    """Set ``exact_backward = mode`` (False, True or "auto") on every ``MSDeformAttn`` below ``model`` (``model`` included);
+    returns how many were set.  See the attribute's comment in ``MSDeformAttn.__init__`` and DESIGN.md 2.12c."""
+    if not (mode is True or mode is False or mode == "auto"):
+        raise ValueError("convert_exact_backward: mode must be False, True or 'auto', got {!r}".format(mode))
+    done = 0
+    for m in model.modules():
+        if isinstance(m, MSDeformAttn):
+            m.exact_backward = mode
+            done += 1
+    return done
